@@ -9,7 +9,15 @@ Philox noise.  A "step" is one full estimator step on one batch: [resample]
 for every step are simulated on the host and uploaded BEFORE the timed region
 (inputs resident in HBM).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, graph
+capture, settle, W warm-up steps, K timed steps, one JSON line (ms_per_step =
+the timed region / K).  --dump-outputs DIR then writes what the last timed step
+computed (dump_outputs) as DIR/<name>.npy; the inputs are seeded, so two runs
+with the same arguments write the same arrays.  --full adds everything else
+the line can carry: the kernel-timing pass (roofline, breakdown_ms_per_step),
+alt_modes, sharded1, strong_single, the secondary rows and the CPU baselines.
 
 N > 1 is launched by torch.distributed.run (one process per GPU) and runs
 --mode sharded by default: the ranks are ONE filter over N x 2^20 particles
@@ -19,7 +27,7 @@ particles, per-rank reduction records) are pushes into peer memory over xGMI
 with device-side signalling, bootstrapped over an RCCL communicator; 8 steps
 per hipGraph, no host decision per step.  --mode replicas runs independent
 Monte-Carlo realisations (no data-path exchange; the N = 1 default).  At N = 1
-the line also carries "sharded1": the sharded step's kernels on one shard, and
+the --full line also carries "sharded1": the sharded step's kernels on one shard, and
 "strong_single": one handle of 2^23 particles (the strong-scaling reference).
 
     --total-particles T   strong scaling: one filter of T particles split over
@@ -596,14 +604,43 @@ def settle(run, ctl, n):
     return n - n % SETTLE_BATCH
 
 
-def timed_runs(filt, ctl, warmup, steps, barrier_sync, ag=None, settle_steps=0):
+DUMP_STATE_MAX = 1 << 20    # --dump-outputs: elements kept per state array (4 x 8 MB)
+
+
+def dump_outputs(path, last, state):
+    """--dump-outputs: what the timed run's last step computed, one float64
+    `<name>.npy` per array -- the fields of the step's record (the last entry
+    of what `run` returns) and the particle set the step left on the device
+    (get_state: x, y, th and the normalised weights).  A state of more than
+    DUMP_STATE_MAX particles is written as a fixed, seeded sample of that
+    many (sorted indices, the same on every run), so a dump stays under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(last[k], dtype=np.float64))
+              for k in ("x_est", "cov", "max_val", "max_idx", "ess", "weight_sum",
+                        "resampled", "resample_next")}
+    n = len(state[0])
+    if n > DUMP_STATE_MAX:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_STATE_MAX, replace=False))
+        state = [a[idx] for a in state]
+    for name, a in zip(("particles_x", "particles_y", "particles_th", "weights"), state):
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def timed_runs(filt, ctl, warmup, steps, barrier_sync, ag=None, settle_steps=0,
+               kernel_timing=True, on_timed=None):
     """Every step graph captured first (graph_capture_ms, never inside a timed
     run), `settle_steps` untimed steps (settle), `warmup` untimed steps, `steps`
     timed steps between barrier + synchronize, then a kernel-timing pass over
     `steps` more steps (HIP events on the filter's stream around every launch).
     ctl holds settle_steps + warmup + 2 steps rows.  With an Agreement (the
     sharded mode) a rank's failure is caught, every rank still reaches every
-    barrier, and the ranks agree on it at the next checkpoint."""
+    barrier, and the ranks agree on it at the next checkpoint.
+    on_timed(filt, out), when given, runs right after the timed steps (the
+    filter still holds their last step's state).  kernel_timing=False (a plain
+    bench run) leaves the kernel-timing pass out: timing is None, and ctl needs
+    settle_steps + warmup + steps rows."""
     call = ag.attempt if ag is not None else (lambda fn, *a, **kw: fn(*a, **kw))
     cap_ms = call(filt.prepare_graphs)
     s0 = call(settle, filt.run, ctl, settle_steps) if settle_steps else 0
@@ -620,6 +657,10 @@ def timed_runs(filt, ctl, warmup, steps, barrier_sync, ag=None, settle_steps=0):
     elapsed = time.perf_counter() - t0
     if ag is not None:
         ag.checkpoint("run")
+    if on_timed is not None:
+        on_timed(filt, out)
+    if not kernel_timing:
+        return elapsed, out, None, cap_ms
     call(filt.enable_timing, True)
     call(filt.run, s0 + warmup + steps, ctl[warmup + steps:warmup + 2 * steps])
     timing = call(lambda: {k: filt.timing(k) for k in range(4)})
@@ -627,6 +668,19 @@ def timed_runs(filt, ctl, warmup, steps, barrier_sync, ag=None, settle_steps=0):
     if ag is not None:
         ag.checkpoint("timing")
     return elapsed, out, timing, cap_ms
+
+
+def index_error_row(fn):
+    """One more measurement of the --full line.  A long run can reach the
+    reference's own IndexError (particle_filter.py:219: a resample position
+    beyond the last cumulative weight; more likely with more particles): the
+    library has then run the batch to its end with the position clamped and the
+    device is sound, so the row reports the error and the rows after it are
+    still measured.  Any other error ends the run."""
+    try:
+        return fn()
+    except IndexError as e:
+        return {"error": f"IndexError: {e}"}
 
 
 def main():
@@ -640,6 +694,14 @@ def main():
                          "(BASELINE configs[2]); replicas (default for N = 1): independent filters")
     ap.add_argument("--total-particles", type=int, default=None,
                     help="strong scaling: one filter of this many particles over the N ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure everything else the line can "
+                         "carry: the kernel-timing pass (roofline, breakdown_ms_per_step), "
+                         "alt_modes, sharded1, strong_single, the secondary rows and the CPU "
+                         "baselines (--no-secondary / --no-cpu-baseline leave those two out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed run's last step computed to DIR/<name>.npy "
+                         "(float64; rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--settle-steps", type=int, default=20 * SETTLE_BATCH,
                     help="untimed steps before the warm-up (whole batches of 31: every graph "
@@ -686,7 +748,10 @@ def main():
     # the NumPy-stream mode refills its word ring once per ~32 requests
     # (kMtRoundsAhead): it is timed over whole refill periods
     ns_steps = max(args.steps, NS_ROUND_STEPS)
-    total_steps = settle_steps + args.warmup + max(2 * args.steps, ns_steps)
+    # (the world is simulated step by step from one seeded stream: a shorter
+    # plain run's rows are the first rows of the --full run's)
+    total_steps = settle_steps + args.warmup + (max(2 * args.steps, ns_steps) if args.full
+                                                else args.steps)
     lm, zs, (vel, omega, dt) = simulate_world(total_steps)
     ctl = np.tile([vel, omega], (total_steps, 1))
 
@@ -698,7 +763,7 @@ def main():
 
     exchange_mode = ["peer"]
 
-    def measure_sharded(likelihood, n_global):
+    def measure_sharded(likelihood, n_global, on_timed=None):
         # one filter over n_global particles (BASELINE configs[2]): this rank's
         # shard through slamhip.dist.DistFilter -- the device-resident step
         # (peer-memory exchanges over xGMI inside the step's kernels, no host
@@ -746,7 +811,8 @@ def main():
             ag.checkpoint("load")
             if multi and os.environ.get("SLAM_BENCH_NO_PARITY") != "1":
                 sharded_parity(filt, ag, n_global, likelihood, kw)
-            return timed_runs(filt, ctl, args.warmup, args.steps, barrier_sync, ag, settle_steps)
+            return timed_runs(filt, ctl, args.warmup, args.steps, barrier_sync, ag, settle_steps,
+                              kernel_timing=args.full, on_timed=on_timed)
         finally:
             if filt is not None:
                 filt.close()
@@ -796,14 +862,15 @@ def main():
             ag.attempt(check)
         ag.checkpoint("parity")
 
-    def measure(likelihood, n_part=None):
+    def measure(likelihood, n_part=None, on_timed=None):
         if args.mode == "sharded":
-            return measure_sharded(likelihood, n_total)
+            return measure_sharded(likelihood, n_total, on_timed)
         pf = DeviceParticleFilter(n_part or n_per_rank, lm, dt=dt, motion="velocity",
                                   likelihood=likelihood, seed=1234 + rank, device=local_rank)
         try:
             pf.load_observations(zs)
-            return timed_runs(pf, ctl, args.warmup, args.steps, barrier_sync, settle_steps=settle_steps)
+            return timed_runs(pf, ctl, args.warmup, args.steps, barrier_sync, settle_steps=settle_steps,
+                              kernel_timing=args.full, on_timed=on_timed)
         finally:
             pf.close()
 
@@ -828,6 +895,12 @@ def main():
         finally:
             pf.close()
 
+    dump = None
+    if args.dump_outputs is not None and rank == 0:
+        def dump(filt, recs):
+            # rank 0's view: the run's last record and the particles it holds
+            dump_outputs(args.dump_outputs, recs[len(recs) - 1], filt.get_state())
+
     sharded_error = None
     if args.mode == "sharded" and multi:
         # the sharded exchange needs every rank's GPU reachable over xGMI; if
@@ -836,7 +909,7 @@ def main():
         # measure independent replicas instead, and the line says so
         # (config.parallelism, sharded_error)
         try:
-            elapsed, out, timing, cap_ms = measure(args.likelihood)
+            elapsed, out, timing, cap_ms = measure(args.likelihood, on_timed=dump)
         except ShardedFailure as e:
             phase, mine = e.args
             print(f"bench: sharded mode failed at {phase} ({mine or 'another rank'})", file=sys.stderr)
@@ -844,13 +917,9 @@ def main():
             dist.all_gather_object(errs, mine)
             sharded_error = f"{phase}: " + ("; ".join(x for x in errs if x) or "another rank failed")
             args.mode = "replicas"
-            elapsed, out, timing, cap_ms = measure(args.likelihood)
+            elapsed, out, timing, cap_ms = measure(args.likelihood, on_timed=dump)
     else:
-        elapsed, out, timing, cap_ms = measure(args.likelihood)
-    fused_ms, fused_n = timing[0]
-    red_ms, red_n = timing[1]
-    res_ms, res_n = timing[2]
-    step_ms, step_n = timing[3]
+        elapsed, out, timing, cap_ms = measure(args.likelihood, on_timed=dump)
 
     if dist is not None:
         import torch
@@ -863,7 +932,6 @@ def main():
     n_rank = n_total // world if args.mode == "sharded" else n_per_rank
     updates = n_job * NL * args.steps
     value = updates / elapsed
-    fused_avg_s = fused_ms / 1e3 / max(fused_n, 1)
     if args.mode == "replicas":
         workload = (f"PF C2: {n_rank:,} particles/GPU x 100 landmarks, velocity motion model, "
                     "systematic resample")
@@ -871,6 +939,7 @@ def main():
         workload = (f"PF C3 form: one filter of {n_job:,} particles sharded {n_rank:,}/GPU x 100 "
                     "landmarks, velocity motion model, exact systematic resample across shards; "
                     "global np.sum-order normalisation")
+    out = list(out)                     # the records as dicts, formed once
     line = {
         "metric": METRIC,
         "value": value,
@@ -888,47 +957,57 @@ def main():
         "config": {"workload": workload, "particles_per_gpu": n_rank, "particles_total": n_job,
                    "landmarks": NL, "likelihood": args.likelihood,
                    "parallelism": f"{args.mode}{world}"},
-        "roofline": fused_roofline(args.likelihood, n_rank, fused_avg_s),
-        "breakdown_ms_per_step": {"fused": fused_ms / max(fused_n, 1),
-                                  "reduce": red_ms / max(red_n, 1),
-                                  "resample": res_ms / max(res_n, 1),
-                                  "step_events": step_ms / max(step_n, 1)},
         "graph_capture_ms": cap_ms,
         "settle_steps": settle_steps,
         "resample_steps": int(sum(o["resampled"] for o in out)),
         "ess_near_steps": int(sum(o.get("ess_near", False) for o in out)),
         "closed_form_fallback_waves": int(sum(o.get("dd_waves", 0) for o in out)),
     }
-    if world == 1 and args.likelihood != "product" and not strong:
+    if timing is not None:
+        # --full: the kernel-timing pass that followed the timed steps
+        (fused_ms, fused_n), (red_ms, red_n), (res_ms, res_n), (step_ms, step_n) = \
+            (timing[k] for k in range(4))
+        line["roofline"] = fused_roofline(args.likelihood, n_rank, fused_ms / 1e3 / max(fused_n, 1))
+        line["breakdown_ms_per_step"] = {"fused": fused_ms / max(fused_n, 1),
+                                         "reduce": red_ms / max(red_n, 1),
+                                         "resample": res_ms / max(res_n, 1),
+                                         "step_events": step_ms / max(step_n, 1)}
+    def row_product():
         e2, _, t2, _ = measure("product")
         f2 = t2[0][0] / 1e3 / max(t2[0][1], 1)
-        line["alt_modes"] = {"product": {"value": n_rank * NL * args.steps / e2,
-                                         "ms_per_step": e2 * 1e3 / args.steps,
-                                         "fused_avg_ms": f2 * 1e3,
-                                         "roofline": fused_roofline("product", n_rank, f2)}}
+        return {"value": n_rank * NL * args.steps / e2, "ms_per_step": e2 * 1e3 / args.steps,
+                "fused_avg_ms": f2 * 1e3, "roofline": fused_roofline("product", n_rank, f2)}
+
+    def row_numpy_stream():
         e4, ring = measure_numpy_stream(args.likelihood)
-        line["alt_modes"]["numpy_stream"] = {
-            "value": NP_PER_GPU * NL * ns_steps / e4, "ms_per_step": e4 * 1e3 / ns_steps,
-            "steps": ns_steps, "ring": ring,
-            "note": "the reference's own noise stream (MT19937 + polar normals, bit-identical to "
-                    "np.random) drawn on the device with the observations simulated there"}
-    if world == 1 and args.mode == "replicas" and not strong:
+        return {"value": NP_PER_GPU * NL * ns_steps / e4, "ms_per_step": e4 * 1e3 / ns_steps,
+                "steps": ns_steps, "ring": ring,
+                "note": "the reference's own noise stream (MT19937 + polar normals, bit-identical to "
+                        "np.random) drawn on the device with the observations simulated there"}
+
+    def row_sharded1():
         # the sharded step's kernels on one shard (its overhead over the single handle)
         e3, _, t3, _ = measure_sharded(args.likelihood, NP_PER_GPU)
-        line["sharded1"] = {"ms_per_step": e3 * 1e3 / args.steps,
-                            "over_single": e3 / elapsed,
-                            "fused_avg_ms": t3[0][0] / max(t3[0][1], 1)}
+        return {"ms_per_step": e3 * 1e3 / args.steps, "over_single": e3 / elapsed,
+                "fused_avg_ms": t3[0][0] / max(t3[0][1], 1)}
+
+    def row_strong_single():
         # strong-scaling reference: one handle of 2^23 particles (BASELINE configs[2]'s
         # total) -- the single-GPU line that `--total-particles 8388608 --gpus N` divides
         e5, o5, t5, _ = measure(args.likelihood, STRONG_TOTAL)
-        line["strong_single"] = {"particles": STRONG_TOTAL,
-                                 "value": STRONG_TOTAL * NL * args.steps / e5,
-                                 "ms_per_step": e5 * 1e3 / args.steps,
-                                 "fused_avg_ms": t5[0][0] / max(t5[0][1], 1),
-                                 "resample_steps": int(sum(o["resampled"] for o in o5))}
-    if rank == 0 and world == 1 and not args.no_secondary and not strong:
+        return {"particles": STRONG_TOTAL, "value": STRONG_TOTAL * NL * args.steps / e5,
+                "ms_per_step": e5 * 1e3 / args.steps, "fused_avg_ms": t5[0][0] / max(t5[0][1], 1),
+                "resample_steps": int(sum(o["resampled"] for o in o5))}
+
+    if args.full and world == 1 and args.likelihood != "product" and not strong:
+        line["alt_modes"] = {"product": index_error_row(row_product)}
+        line["alt_modes"]["numpy_stream"] = index_error_row(row_numpy_stream)
+    if args.full and world == 1 and args.mode == "replicas" and not strong:
+        line["sharded1"] = index_error_row(row_sharded1)
+        line["strong_single"] = index_error_row(row_strong_single)
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not strong:
         line["secondary"] = secondary(local_rank, cpu=not args.no_cpu_baseline)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not strong:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not strong:
         line["cpu_baseline"] = cpu_baseline()
         line["cpu_baseline"]["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
         try:

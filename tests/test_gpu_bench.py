@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_bench_json_contract():
     env = dict(os.environ)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8",
-                        "--warmup", "2", "--no-secondary", "--no-cpu-baseline"],
+                        "--warmup", "2", "--full", "--no-secondary", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=100)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -40,6 +40,43 @@ def test_bench_json_contract():
     assert d["config"]["particles_per_gpu"] == 2 ** 20 and d["config"]["landmarks"] == 100
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline fields and none of the --full
+    measurements; --dump-outputs writes the last timed step's record and
+    particle set as float64 .npy files (at most 64 MB), the same arrays on a
+    second run with the same arguments."""
+    import numpy as np
+    names = {"x_est": (3,), "cov": (3, 3), "max_val": (1,), "max_idx": (1,), "ess": (1,),
+             "weight_sum": (1,), "resampled": (1,), "resample_next": (1,),
+             "particles_x": (2 ** 20,), "particles_y": (2 ** 20,), "particles_th": (2 ** 20,),
+             "weights": (2 ** 20,)}
+    dumps = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        d = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6",
+                         "--warmup", "2", "--settle-steps", "62", "--dump-outputs", str(out)])
+        assert d["steps"] == 6 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["unit"] == "particle-observation updates/s" and d["value"] > 1e10
+        assert abs(d["value"] - 2 ** 20 * 100 / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+        for key in ("roofline", "breakdown_ms_per_step", "alt_modes", "sharded1", "strong_single",
+                    "secondary", "cpu_baseline", "cpu_baseline_vectorised"):
+            assert key not in d, key
+        assert sorted(p.name for p in out.iterdir()) == sorted(n + ".npy" for n in names)
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2 ** 20
+        arrs = {n: np.load(out / (n + ".npy")) for n in names}
+        for n, shape in names.items():
+            assert arrs[n].dtype == np.float64 and arrs[n].shape == shape, n
+        dumps.append(arrs)
+    a, b = dumps
+    for n in names:
+        assert np.array_equal(a[n], b[n]), n
+    assert all(np.isfinite(a[n]).all() for n in names)
+    # the record describes the particle set beside it
+    i = int(a["max_idx"][0])
+    assert a["weights"][i] == a["weights"].max() == a["max_val"][0]
+    assert abs(np.sum(a["weights"]) - 1.0) < 1e-9 and np.all(a["weights"] >= 0)
+
+
 def _bench_line(cmd):
     r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True,
                        timeout=110)
@@ -54,7 +91,7 @@ def test_bench_sharded_mode(launcher):
     # --mode sharded: the device-resident sharded step over one shard, in-process
     # or as a 1-rank group under torch.distributed.run
     args = [os.path.join(ROOT, "bench.py"), "--mode", "sharded", "--steps", "6", "--warmup", "2",
-            "--no-secondary", "--no-cpu-baseline"]
+            "--full", "--no-secondary", "--no-cpu-baseline"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                "--master-addr", "127.0.0.1", "--master-port", "29533"] + args
