@@ -167,6 +167,56 @@ int slam_pf_set_ess_band(slam_pf* h, double band);
 int slam_pf_set_stream(slam_pf* h, void* hip_stream, int32_t external);
 
 /* ====================================================================
+ * Particle-filter ensemble -- n_filters independent ParticleFilter instances
+ * (particle_filter.py:18-237) of n_particles <= 8192 each (the reference's
+ * NP = 1000): Monte-Carlo repetitions over seeds or maps, parameter sweeps,
+ * one filter per robot.  The filters share NP, NL, the motion model, the
+ * likelihood form and dt; landmarks, R, the noise map / alphas, x0, the ESS
+ * threshold and the seed are per filter (cfgs[b]).  One workgroup runs one
+ * filter's whole step, and a run of any number of steps is one launch.
+ * Filter b with device noise draws the stream of a slam_pf created from
+ * cfgs[b] (n_global = NP): its particles, weights, np.sum, maximum and
+ * estimate are bit-identical to that handle's (SLAM_LIK_PRODUCT; the log-sum
+ * form here is the landmark loop, not the closed-form expansion).
+ * Arrays carry a leading filter axis.  A filter's resample clamp (the
+ * reference's IndexError) sets bit 0 of its record's status and does not fail
+ * the call; a flagged exact-cumsum fallback sets bit 1.
+ * ==================================================================== */
+typedef struct slam_pfb slam_pfb;
+/* cfgs: n_filters records; motion, likelihood and dt must agree across them
+ * (SLAM_ERR_ARG otherwise).  landmarks: n_filters x n_landmarks x 2.
+ * 1 <= n_particles <= 8192, n_landmarks >= 1. */
+int slam_pfb_create(const slam_pf_config* cfgs, int32_t n_filters, int32_t n_particles,
+                    int32_t n_landmarks, const double* landmarks, int device, slam_pfb** out);
+int slam_pfb_destroy(slam_pfb* h);
+int slam_pfb_info(slam_pfb* h, int32_t* n_filters, int32_t* n_particles, int32_t* n_landmarks);
+/* arrays [n_filters][n_particles]; any pointer may be NULL (left unchanged / not read).
+ * Setting w also sets every filter's next resample decision from it (:210-211). */
+int slam_pfb_set_state(slam_pfb* h, const double* x, const double* y, const double* th,
+                       const double* w);
+int slam_pfb_get_state(slam_pfb* h, double* x, double* y, double* th, double* w);
+/* like slam_pf_get_weights_raw: w_un [B][NP], s [B] */
+int slam_pfb_get_weights_raw(slam_pfb* h, double* w_un, double* s);
+/* per-filter override of the next step's resample decision: flags[B], -1 keeps the device's */
+int slam_pfb_set_resample_next(slam_pfb* h, const int32_t* flags);
+int slam_pfb_set_ess_band(slam_pfb* h, double band);
+/* one step of every filter: control [B][2], z [B][NL][2], noise [B][NP][3] or NULL
+ * (device RNG), u_resample [B] or NULL (NaN entries / NULL: device RNG), res [B] */
+int slam_pfb_step(slam_pfb* h, const double* control, const double* z, const double* noise,
+                  const double* u_resample, slam_pf_result* res);
+/* device-resident: z_all [n_steps][B][NL][2]; controls [n_steps][B][2] (the steps of
+ * this call); results [n_steps][B].  One launch per run call, no hipGraph. */
+int slam_pfb_load_observations(slam_pfb* h, int32_t n_steps, const double* z_all);
+int slam_pfb_run(slam_pfb* h, int32_t first_step, int32_t n_steps, const double* controls,
+                 slam_pf_result* results);
+/* exact systematic-resampling indices of every filter's CURRENT weights: idx [B][NP]
+ * (u_resample as in slam_pfb_step).  SLAM_ERR_INDEX, with the indices filled and
+ * clamped, when a filter's position lies beyond its last cumulative weight. */
+int slam_pfb_resample_indices(slam_pfb* h, const double* u_resample, int64_t* idx_out);
+/* HIP-event time of the last step / run call (ms) and its launches (always 1) */
+int slam_pfb_timing(slam_pfb* h, double* ms, int64_t* launches);
+
+/* ====================================================================
  * MotionModel -- replaces motion_model.py:14-86 for a batch of poses
  * (batch = 1 is the reference's single call).
  *   params:  dt, a1..a6                                   (motion_model.py:20-29)

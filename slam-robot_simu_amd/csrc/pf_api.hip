@@ -149,53 +149,7 @@ int dalloc(slam_pf* h, T** p, size_t count) {
     return halloc(h, (void**)p, count * sizeof(T));
 }
 
-int make_lik_const(slam_pf* h) {
-    // particle_filter.py:179-181 and the bivariate_normal constants, in numpy's order
-    const double* R = h->cfg.r_cov;
-    LikConst& lc = h->lc;
-    const double sx = std::sqrt(R[0]), sy = std::sqrt(R[3]), sxy = std::sqrt(R[1]);
-    if (!(sx > 0) || !(sy > 0) || std::isnan(sxy))
-        return fail(SLAM_ERR_ARG, "r_cov: need R00 > 0, R11 > 0, R01 >= 0");
-    const double rho = sxy / (sx * sy);
-    lc.sx2 = sx * sx;
-    lc.sy2 = sy * sy;
-    lc.rsx2 = 1.0 / lc.sx2;
-    lc.rsy2 = 1.0 / lc.sy2;
-    lc.rho2 = 2 * rho;
-    lc.sxsy = sx * sy;
-    lc.d2 = 2 * (1 - rho * rho);
-    lc.den = 2 * kPi * sx * sy * std::sqrt(1 - rho * rho);
-    lc.rden = 1.0 / lc.den;
-    lc.nl = h->nl;
-    lc.neg_nl_ln_den = -(double)h->nl * std::log(lc.den);
-    lc.has_rho = (rho != 0.0) ? 1 : 0;
-    lc.rsxsy = 1.0 / lc.sxsy;
-    lc.rd2 = 1.0 / lc.d2;
-    lc.iso = (lc.sx2 == lc.sy2 && !lc.has_rho) ? 1 : 0;
-    // closed-form log-sum (iso, NL > 0); SLAM_PF_CLOSED=0 keeps the landmark loop (diagnostic)
-    const char* ce = std::getenv("SLAM_PF_CLOSED");
-    lc.closed = (lc.iso && h->nl > 0 && !(ce && ce[0] == '0')) ? 1 : 0;
-    // Log-sum fast-path bound.  A factor is at most 1/den (q >= 0), so the log of
-    // the reference's partial product after landmark k is at least
-    // L - (NL - k) max(0, -ln den).  L >= ln(DBL_MIN) + NL max(0, -ln den) + 1
-    // keeps every partial product of particle_filter.py:192 in the normal range
-    // (the 1-nat margin covers the rounding of both sums); below it the kernel
-    // takes the reference's sequential product.  Past NL max(0, -ln den) = 700
-    // the products may overflow: always the sequential product.
-    const double climb = (double)h->nl * std::max(0.0, -std::log(lc.den));
-    lc.normal_min_l = std::log(std::numeric_limits<double>::min()) + 1.0;
-    lc.neg_ln_den = -std::log(lc.den);
-    lc.fast_min_l = climb > 700.0 ? std::numeric_limits<double>::infinity()
-                                  : lc.normal_min_l + climb;
-    // closed form: the fp64 expansion while its rounding bound 11 u V stays
-    // within |dL| <= 3e-13 (dL = dF / (2 sx2), under a third of the 1e-12
-    // parity bar): V rsx2 <= 480; SLAM_PF_EXPAND_VMAX=<factor>
-    // scales the bound (0: double-double only)
-    const char* ve = std::getenv("SLAM_PF_EXPAND_VMAX");
-    const double vf = ve ? std::atof(ve) : 1.0;
-    lc.expand_vmax = vf * 480.0 * lc.sx2;
-    return SLAM_OK;
-}
+int make_lik_const(slam_pf* h) { return lik_const_from(h->cfg.r_cov, h->nl, true, h->lc); }
 
 void make_predict_const(slam_pf* h) {
     PredictConst& pc = h->pc;

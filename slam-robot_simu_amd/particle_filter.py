@@ -130,6 +130,81 @@ class ParticleFilter(object):
         return self.dev.get_state()[3]
 
 
+class ParticleFilterEnsemble(object):
+    """``n_filters`` realisations of ``ParticleFilter(period_ms, ...)`` advanced
+    together on one GPU (slamhip.pf_batch.BatchParticleFilter: one workgroup per
+    filter, one launch per step) -- Monte-Carlo repetitions over noise seeds or
+    landmark maps.  Truth and observation stay on the host, from one
+    ``RandomState(seed + b)`` per filter drawn in the reference's order
+    ([rand() if resampling] -> mvn(0, Q, NP) -> observation noise), so filter b
+    does not depend on how many filters run beside it.
+
+    ``landmarks``: (NL, 2) for every filter or (n_filters, NL, 2).
+    ``noise="numpy"``: motion noise from the filter's RandomState;
+    ``noise="device"``: Philox on the GPU (key ``seed + b``).
+    ``main_pf()`` returns the reference's tuple with a leading filter axis."""
+
+    def __init__(self, period_ms, n_filters, *, n_particles=1000, landmarks=None, noise="numpy",
+                 motion="linear", likelihood="product", alphas=(0.1,) * 6, seed=0, device=0):
+        from slamhip.pf_batch import BatchParticleFilter
+        self.period_ms = period_ms
+        self.n_filters = B = int(n_filters)
+        self.dt = period_ms / 1000                                 # :30
+        self.n_particles = int(n_particles)                        # :31
+        lm = DEFAULT_LANDMARKS.copy() if landmarks is None else np.asarray(landmarks, float)
+        self.lm = np.ascontiguousarray(np.broadcast_to(lm, (B,) + lm.shape[-2:]))
+        self.radius = 10.0                                         # :46
+        self.yaw_rate = np.deg2rad(10.0)                           # :47
+        self.vel = self.radius * self.yaw_rate                     # :48
+        self.Q = np.diag([0.03, 0.03, np.deg2rad(2.0)]) ** 2        # :62-65
+        self.R = np.diag([0.3, 0.3]) ** 2                          # :68-70
+        x0 = np.array([[self.radius], [0.0], [np.deg2rad(90.0)]])  # :74-79
+        self.x_true = np.tile(x0, (B, 1, 1))
+        if noise not in ("numpy", "device"):
+            raise ValueError("noise must be 'numpy' or 'device'")
+        self.noise = noise
+        self.motion = motion
+        self.alphas = tuple(alphas)
+        self.rng = [np.random.RandomState(int(seed) + b) for b in range(B)]
+        self.dev = BatchParticleFilter(
+            B, self.n_particles, self.lm, dt=self.dt, q=self.Q, r=self.R, x0=x0[:, 0], motion=motion,
+            likelihood=likelihood, alphas=alphas, seed=int(seed) + np.arange(B), device=device)
+        self.last = None
+
+    def main_pf(self):
+        """particle_filter.py:86-119 for every filter -> (LM [B][NL][2], x_true
+        [B][3][1], x_est [B][3][1], px [B][3][NP], Q, max_idx [B], max_val [B])."""
+        B, n = self.n_filters, self.n_particles
+        resampling = self.dev.resample_next
+        u = np.full(B, np.nan)
+        noise = None if self.noise == "device" else np.empty((B, n, 3))
+        z = np.empty((B, self.lm.shape[1], 2))
+        for b, rs in enumerate(self.rng):
+            self.x_true[b] = ParticleFilter._truth_step(self, self.x_true[b])
+            if self.noise == "numpy":
+                if resampling[b]:
+                    u[b] = rs.rand()                                               # :214
+                if self.motion == "linear":
+                    noise[b] = rs.multivariate_normal([0.0, 0.0, 0.0], self.Q, n)  # :165
+                else:
+                    noise[b] = rs.standard_normal(3 * n).reshape(n, 3)             # motion_model.py:46-48
+            zb = tf.world2robot(self.x_true[b], self.lm[b])
+            z[b] = zb + rs.multivariate_normal([0.0, 0.0], self.R, zb.shape[0])    # :151-153
+        ctl = (self.vel, self.yaw_rate)
+        self.last = outs = self.dev.step(ctl, z, noise, u)
+        x, y, th, _ = self.dev.get_state()
+        return (self.lm, self.x_true.copy(), np.array([o["x_est"] for o in outs]).reshape(B, 3, 1),
+                np.stack([x, y, th], axis=1), self.Q, np.array([o["max_idx"] for o in outs]),
+                np.array([o["max_val"] for o in outs]))
+
+    @property
+    def weights(self):
+        return self.dev.get_state()[3]
+
+    def close(self):
+        self.dev.close()
+
+
 # ---------------------------------------------------------------- animation
 class PFAnimation:
     """The reference's demo frame (particle_filter.py:248-327) over this

@@ -102,6 +102,20 @@ SIGNATURES = {
     "slam_pf_set_ess_band": (C.c_int, [_P, C.c_double]),
     "slam_pf_set_resample_next": (C.c_int, [_P, C.c_int32]),
     "slam_pf_set_stream": (C.c_int, [_P, _P, C.c_int32]),
+    "slam_pfb_create": (C.c_int, [C.POINTER(PFConfig), C.c_int32, C.c_int32, C.c_int32, _D, C.c_int,
+                                  C.POINTER(_P)]),
+    "slam_pfb_destroy": (C.c_int, [_P]),
+    "slam_pfb_info": (C.c_int, [_P, _I32, _I32, _I32]),
+    "slam_pfb_set_state": (C.c_int, [_P, _D, _D, _D, _D]),
+    "slam_pfb_get_state": (C.c_int, [_P, _D, _D, _D, _D]),
+    "slam_pfb_get_weights_raw": (C.c_int, [_P, _D, _D]),
+    "slam_pfb_set_resample_next": (C.c_int, [_P, _I32]),
+    "slam_pfb_set_ess_band": (C.c_int, [_P, C.c_double]),
+    "slam_pfb_step": (C.c_int, [_P, _D, _D, _D, _D, C.POINTER(PFResult)]),
+    "slam_pfb_load_observations": (C.c_int, [_P, C.c_int32, _D]),
+    "slam_pfb_run": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.POINTER(PFResult)]),
+    "slam_pfb_resample_indices": (C.c_int, [_P, _D, _I64]),
+    "slam_pfb_timing": (C.c_int, [_P, _D, _I64]),
     "slam_motion_velocity": (C.c_int, [_D, C.c_int64, _D, C.c_double, C.c_double, _D, _D,
                                        C.c_int]),
     "slam_scan_detect": (C.c_int, [C.c_int64, _D, _D, C.c_int64, _D, C.c_double, C.c_double, _I32, _D,
