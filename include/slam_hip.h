@@ -400,6 +400,99 @@ int slam_ekfslam_step(slam_ekfslam* h, const double* control, int32_t k, const i
 int slam_ekfslam_timing(slam_ekfslam* h, double* out);
 
 /* ====================================================================
+ * FastSLAM 1.0 with known data association (an extension: the reference's
+ * particle filter localises against a known map).  Every particle carries a
+ * pose, a weight and, per landmark, a mean (mx, my) and a symmetric 2 x 2
+ * covariance (pxx, pxy, pyy) -- one small EKF per particle and landmark.  A
+ * step observes any k <= NL landmarks (ScanSensor's range, bearing,
+ * orientation; graph_based_slam.py:150-153) with known ids; whether a landmark
+ * has been seen is a property of the filter, not of the particle.
+ *
+ * One step, in the reference's order (particle_filter.py:102-117):
+ *   1. resample if the previous step's ESS < ESS_TH: slam_pf's exact systematic
+ *      resampling; the gather moves the pose and the map rows of every seen
+ *      landmark;
+ *   2. predict: slam_pf's (linear or velocity motion, host noise or the
+ *      handle's Philox stream with slam_pf's counters);
+ *   3. per observation t in the order given (landmark j, z = (d, phi, psi)),
+ *      psi_p = pi/2 - theta_p, R = diag((d r_dist)^2, (d sin r_dir)^2):
+ *      orientation term (use_orient): e = wrap(psi - wrap(psi_p)),
+ *      L_p -= e^2 / (2 (r_dir^2 + r_orient^2));
+ *      j unseen: mean = pose + Rot(psi_p)^T (d cos phi, d sin phi), covariance
+ *      through the inverse landmark Jacobian, no weight term;
+ *      j seen: EKF update with H = d(range, bearing)/d(landmark),
+ *      S = H P H^T + R, L_p -= (e^T S^-1 e + ln det S) / 2, K = P H^T S^-1,
+ *      mean += K e, P <- P - K S K^T;
+ *   4. w_un = w exp(L_p - max_p L_p) (log domain: a product of 300 densities
+ *      overflows fp64);
+ *   5. slam_pf's step end (np.sum-order sum, normalise, argmax, estimate,
+ *      weighted covariance, ESS, resample_next, ess_near) into one
+ *      slam_pf_result whose weight_sum is the sum of the shifted w_un.
+ * ==================================================================== */
+typedef struct slam_fs slam_fs;
+
+typedef struct {
+    slam_pf_config pf;    /* dt, ess_threshold, q_factor, alphas, x0, seed, motion;
+                             r_cov and likelihood are ignored */
+    double r_dist;        /* ScanSensor range noise fraction (graph_based_slam.py:187-192) */
+    double r_dir;         /* bearing noise (rad) */
+    double r_orient;      /* orientation noise (rad) */
+    int32_t use_orient;   /* weigh the observed orientation against the particle's heading */
+    int32_t pad0;
+} slam_fs_config;
+
+/* The argument rules of one step's observations, without a handle or a device:
+ * SLAM_ERR_ARG for k < 0, k > n_landmarks, an id outside [0, n_landmarks), a
+ * duplicate id, d <= 0 or a non-finite value.  slam_fs_step, slam_fs_update
+ * and slam_fs_load_observations apply the same rules before any HIP call. */
+int slam_fs_check_observations(int32_t n_landmarks, int32_t k, const int64_t* ids, const double* obs);
+
+/* 1 <= n_particles <= 2^24, n_landmarks >= 1; the two map halves take
+ * 2 x 40 B x n_landmarks x n_particles (SLAM_ERR_HIP when they do not fit). */
+int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_landmarks, int device,
+                   slam_fs** out);
+int slam_fs_destroy(slam_fs* h);
+/* any pointer may be NULL; n_seen: landmarks observed so far */
+int slam_fs_info(slam_fs* h, int64_t* n_particles, int32_t* n_landmarks, int32_t* n_seen);
+
+/* x, y, th, w as slam_pf_set_state / slam_pf_get_state */
+int slam_fs_set_state(slam_fs* h, const double* x, const double* y, const double* th,
+                      const double* w);
+int slam_fs_get_state(slam_fs* h, double* x, double* y, double* th, double* w);
+int slam_fs_set_resample_next(slam_fs* h, int32_t on);
+/* seen[NL] (int32), mean[NP][NL][2], cov[NP][NL][3] (pxx, pxy, pyy) */
+int slam_fs_set_maps(slam_fs* h, const int32_t* seen, const double* mean, const double* cov);
+/* any pointer may be NULL; unseen landmarks come back as NaN */
+int slam_fs_get_maps(slam_fs* h, int32_t* seen, double* mean, double* cov);
+/* one particle's map, O(NL): mean[NL][2], cov[NL][3].  The map estimate is
+ * the map of slam_pf_result.max_idx, as x_est is its pose. */
+int slam_fs_get_map(slam_fs* h, int64_t particle, int32_t* seen, double* mean, double* cov);
+
+/* control (v, omega); k observations: ids[k], obs[k][3] (range, bearing,
+ * orientation); noise and u_resample as slam_pf_step. */
+int slam_fs_step(slam_fs* h, const double* control, int32_t k, const int64_t* ids, const double* obs,
+                 const double* noise, double u_resample, slam_pf_result* res);
+/* Stages: resample (force != 0: whatever the flag), predict, map update +
+ * weights + step end on the current particles. */
+int slam_fs_resample(slam_fs* h, double u_resample, int32_t force, int32_t* resampled);
+int slam_fs_predict(slam_fs* h, const double* control, const double* noise);
+int slam_fs_update(slam_fs* h, int32_t k, const int64_t* ids, const double* obs,
+                   slam_pf_result* res);
+
+/* Multi-step run: the observations of n_steps steps are uploaded once
+ * (counts[n_steps]; ids and obs hold the steps' lists one after the other),
+ * slam_fs_run steps through [first_step, first_step + n_steps) with the
+ * device RNG; results identical to slam_fs_step called in turn (noise NULL,
+ * u_resample NaN).  The host reads the resample flag once per step. */
+int slam_fs_load_observations(slam_fs* h, int32_t n_steps, const int32_t* counts, const int64_t* ids,
+                              const double* obs);
+int slam_fs_run(slam_fs* h, int32_t first_step, int32_t n_steps, const double* controls,
+                slam_pf_result* results);
+/* HIP-event time (ms) of the last step's phases: out[4] = {map gather, predict,
+ * map update + weights, step end}; 0 for a phase that did not run. */
+int slam_fs_timing(slam_fs* h, double* out);
+
+/* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve
  * (graph_based_slam.py: setPairObs :362-439, updateEstPose :452-514) and
  * the Gauss-Newton loop of Robot.estimateOpticalTrajectory (:685-715).

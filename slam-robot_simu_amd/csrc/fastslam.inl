@@ -1,0 +1,225 @@
+// fastslam.inl -- gfx950 kernels of FastSLAM 1.0 with known data association
+// (included by fs_api.inl): the per-particle landmark EKFs with their log
+// weights, the weight pass, and the resampling gather of whole maps.
+//
+// Map layout: component-major per landmark,
+//     map[(5 j + c) * npad + p],   c = mx, my, pxx, pxy, pyy
+// so that a wave's 64 particles read and write 512 contiguous bytes per
+// component in the update, and the gather -- whose source indices are
+// non-decreasing in p -- reads neighbouring or equal addresses.
+namespace slam {
+
+constexpr int kFsThreads = 256;
+constexpr int kFsObsLds = 128;      // observations staged per pass (9.3 KB of LDS)
+constexpr int kFsComp = 5;
+
+// One observation with its particle-independent terms (formed on the host
+// once per step, or once per loaded run)
+struct FsObs {
+    double d, phi, psi;     // range, bearing, orientation
+    double r0, r1;          // (d r_dist)^2, (d sin r_dir)^2
+    double rx, ry;          // d cos phi, d sin phi
+    double vo;              // r_dir^2 + r_orient^2
+    int64_t id;
+};
+
+__device__ __forceinline__ double fs_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// One lane per particle, a loop over the step's observations (staged in LDS
+// kFsObsLds at a time).  Writes the particle's log weight L and the block's
+// maximum of L.
+__global__ __launch_bounds__(kFsThreads) void fs_update_kernel(
+    const int64_t n, const int64_t npad, const double* __restrict__ xs,
+    const double* __restrict__ ys, const double* __restrict__ ts, double* __restrict__ map,
+    const int32_t nobs, const FsObs* __restrict__ obs, const int32_t* __restrict__ seen,
+    const int32_t use_orient, double* __restrict__ L_out, double* __restrict__ bmax) {
+    __shared__ double s_d[kFsObsLds], s_phi[kFsObsLds], s_psi[kFsObsLds], s_r0[kFsObsLds],
+        s_r1[kFsObsLds], s_rx[kFsObsLds], s_ry[kFsObsLds], s_vo[kFsObsLds];
+    __shared__ int64_t s_id[kFsObsLds];
+    __shared__ int32_t s_seen[kFsObsLds];
+    __shared__ double s_wmax[kFsThreads / 64];
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    const bool valid = p < n;
+    const int64_t pc = valid ? p : n - 1;
+    const double x = xs[pc], y = ys[pc], th = ts[pc];
+    const double psi_p = kHalfPi - th;
+    double s, c;
+    sincos(psi_p, &s, &c);
+    const double psi_w = wrap_angle(psi_p);
+    double L = 0.0;
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t cnt = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        __syncthreads();
+        if ((int32_t)threadIdx.x < cnt) {
+            const FsObs o = obs[base + threadIdx.x];
+            s_d[threadIdx.x] = o.d;
+            s_phi[threadIdx.x] = o.phi;
+            s_psi[threadIdx.x] = o.psi;
+            s_r0[threadIdx.x] = o.r0;
+            s_r1[threadIdx.x] = o.r1;
+            s_rx[threadIdx.x] = o.rx;
+            s_ry[threadIdx.x] = o.ry;
+            s_vo[threadIdx.x] = o.vo;
+            s_id[threadIdx.x] = o.id;
+            s_seen[threadIdx.x] = seen[o.id];
+        }
+        __syncthreads();
+        for (int32_t t = 0; t < cnt; ++t) {
+            const double R0 = s_r0[t], R1 = s_r1[t];
+            double* m = map + (size_t)kFsComp * (size_t)s_id[t] * (size_t)npad + (size_t)pc;
+            if (use_orient) {
+                const double e = wrap_angle(s_psi[t] - psi_w);
+                L -= e * e / (2.0 * s_vo[t]);
+            }
+            if (!s_seen[t]) {
+                // first sighting: the observation placed in the world, and its
+                // covariance through the inverse of the landmark Jacobian
+                const double rx = s_rx[t], ry = s_ry[t];
+                const double dx = c * rx + s * ry, dy = -s * rx + c * ry;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double a00 = dx / r, a01 = -dy, a10 = dy / r, a11 = dx;
+                if (valid) {
+                    m[0] = x + dx;
+                    m[(size_t)npad] = y + dy;
+                    m[2 * (size_t)npad] = a00 * a00 * R0 + a01 * a01 * R1;
+                    m[3 * (size_t)npad] = a00 * a10 * R0 + a01 * a11 * R1;
+                    m[4 * (size_t)npad] = a10 * a10 * R0 + a11 * a11 * R1;
+                }
+                continue;
+            }
+            const double mx = m[0], my = m[(size_t)npad];
+            const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                         pyy = m[4 * (size_t)npad];
+            const double dx = mx - x, dy = my - y;
+            const double q = dx * dx + dy * dy, r = sqrt(q);
+            const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+            const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+            const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+            const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+            const double s00 = h00 * t00 + h01 * t10 + R0;
+            const double s01 = h00 * t01 + h01 * t11;
+            const double s11 = h10 * t01 + h11 * t11 + R1;
+            const double det = s00 * s11 - s01 * s01;
+            const double e0 = s_d[t] - r, e1 = wrap_angle(s_phi[t] - bearing);
+            const double maha = (e0 * e0 * s11 - 2.0 * (e0 * e1) * s01 + e1 * e1 * s00) / det;
+            L -= (maha + log(det)) / 2.0;
+            const double k00 = (t00 * s11 - t01 * s01) / det, k01 = (t01 * s00 - t00 * s01) / det;
+            const double k10 = (t10 * s11 - t11 * s01) / det, k11 = (t11 * s00 - t10 * s01) / det;
+            const double m00 = k00 * s00 + k01 * s01, m01 = k00 * s01 + k01 * s11;
+            const double m10 = k10 * s00 + k11 * s01, m11 = k10 * s01 + k11 * s11;
+            if (valid) {
+                m[0] = mx + (k00 * e0 + k01 * e1);
+                m[(size_t)npad] = my + (k10 * e0 + k11 * e1);
+                m[2 * (size_t)npad] = pxx - (m00 * k00 + m01 * k01);
+                m[3 * (size_t)npad] = pxy - (m00 * k10 + m01 * k11);
+                m[4 * (size_t)npad] = pyy - (m10 * k10 + m11 * k11);
+            }
+        }
+    }
+    if (valid) L_out[p] = L;
+    const double wm = fs_wave_max(valid ? L : -INFINITY);
+    if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = wm;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = s_wmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) v = fmax(v, s_wmax[w]);
+        bmax[blockIdx.x] = v;
+    }
+}
+
+// The grid maximum: a plain fold of the block maxima (the maximum is
+// order-free, so it is deterministic; no floating-point atomics)
+__global__ __launch_bounds__(kFsThreads) void fs_max_fold_kernel(const double* __restrict__ bmax,
+                                                                 const int32_t nb,
+                                                                 double* __restrict__ gmax) {
+    __shared__ double s_wmax[kFsThreads / 64];
+    double v = -INFINITY;
+    for (int32_t b = threadIdx.x; b < nb; b += kFsThreads) v = fmax(v, bmax[b]);
+    v = fs_wave_max(v);
+    if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = s_wmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) v = fmax(v, s_wmax[w]);
+        *gmax = v;
+    }
+}
+
+// w_un = w exp(L - max L): the weights in the log domain (a product of k
+// densities overflows fp64 near k = 300)
+__global__ __launch_bounds__(kFsThreads) void fs_weight_kernel(const int64_t n,
+                                                               const double* __restrict__ L,
+                                                               const double* __restrict__ gmax,
+                                                               double* __restrict__ w_un) {
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= n) return;
+    w_un[p] = w_un[p] * exp(L[p] - *gmax);
+}
+
+__global__ __launch_bounds__(kFsThreads) void fs_mark_seen_kernel(const int32_t nobs,
+                                                                  const FsObs* __restrict__ obs,
+                                                                  int32_t* __restrict__ seen) {
+    const int32_t t = (int32_t)(blockIdx.x * kFsThreads + threadIdx.x);
+    if (t < nobs) seen[obs[t].id] = 1;
+}
+
+// Resampling gather of the maps: particle p of the other ping-pong half takes
+// the rows of its source idx[p] for every seen landmark (list[0..nlist)).
+// blockIdx.y walks the seen landmarks; idx is non-decreasing, so the lanes of
+// a wave read neighbouring or equal addresses in each of the five components.
+__global__ __launch_bounds__(kFsThreads) void fs_map_gather_kernel(
+    const int64_t n, const int64_t npad, const int32_t* __restrict__ idx,
+    const int32_t* __restrict__ list, const int32_t nlist, const double* __restrict__ src,
+    double* __restrict__ dst) {
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= n) return;
+    const int64_t q = idx[p];
+    for (int32_t k = blockIdx.y; k < nlist; k += gridDim.y) {
+        const size_t row = (size_t)kFsComp * (size_t)list[k] * (size_t)npad;
+        const double* a = src + row + (size_t)q;
+        double* b = dst + row + (size_t)p;
+        const double v0 = a[0], v1 = a[(size_t)npad], v2 = a[2 * (size_t)npad],
+                     v3 = a[3 * (size_t)npad], v4 = a[4 * (size_t)npad];
+        b[0] = v0;
+        b[(size_t)npad] = v1;
+        b[2 * (size_t)npad] = v2;
+        b[3 * (size_t)npad] = v3;
+        b[4 * (size_t)npad] = v4;
+    }
+}
+
+// host layout [NP][NL][ncomp] <-> component-major device layout; comp0 = 0
+// (the means, ncomp 2) or 2 (the covariances, ncomp 3).  An unseen landmark
+// reads back as NaN.
+__global__ __launch_bounds__(kFsThreads) void fs_map_pack_kernel(
+    const int64_t n, const int64_t npad, const int32_t nl, const int64_t p0, const int64_t count,
+    const int32_t comp0, const int32_t ncomp, const int32_t* __restrict__ seen,
+    const double* __restrict__ map, double* __restrict__ out) {
+    const int64_t p = p0 + (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= p0 + count || p >= n) return;
+    for (int32_t j = blockIdx.y; j < nl; j += gridDim.y) {
+        const bool sj = seen[j] != 0;
+        for (int32_t c = 0; c < ncomp; ++c)
+            out[((size_t)(p - p0) * nl + j) * ncomp + c] =
+                sj ? map[((size_t)kFsComp * j + comp0 + c) * (size_t)npad + (size_t)p] : NAN;
+    }
+}
+
+__global__ __launch_bounds__(kFsThreads) void fs_map_unpack_kernel(
+    const int64_t n, const int64_t npad, const int32_t nl, const int32_t comp0, const int32_t ncomp,
+    const double* __restrict__ in, double* __restrict__ map) {
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= n) return;
+    for (int32_t j = blockIdx.y; j < nl; j += gridDim.y)
+        for (int32_t c = 0; c < ncomp; ++c)
+            map[((size_t)kFsComp * j + comp0 + c) * (size_t)npad + (size_t)p] =
+                in[((size_t)p * nl + j) * ncomp + c];
+}
+
+}  // namespace slam

@@ -1,0 +1,509 @@
+// fs_api.inl -- C-ABI of FastSLAM 1.0 with known data association
+// (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
+// pf_dist_api.inl is: the poses, weights, exact cumsum, systematic resampling,
+// predict and step end are the single handle's own (a slam_pf with zero
+// landmarks); this file adds the per-particle maps, their update with its log
+// weights, and their resampling gather (fastslam.inl).
+#include "fastslam.inl"
+
+struct slam_fs {
+    slam_fs_config cfg;
+    slam_pf* pf = nullptr;
+    int64_t n = 0, npad = 0;
+    int32_t nl = 0;
+    double* map[2] = {nullptr, nullptr};   // ping-pong halves, [NL][5][npad]
+    int mcur = 0;
+    double* L = nullptr;                   // [n] log weights of the step
+    double* bmax = nullptr;                // [nb] block maxima, then the grid maximum at [nb]
+    int32_t nb = 0;
+    int32_t* seen_dev = nullptr;           // [NL]
+    int32_t* list_dev = nullptr;           // [NL] the seen landmarks (gather)
+    FsObs* obs_dev = nullptr;              // the staged step, or the loaded run
+    int64_t obs_cap = 0;
+    double* stage = nullptr;               // get / set maps staging
+    int64_t stage_cap = 0;                 // doubles
+    std::vector<int32_t> seen;             // host mirror
+    std::vector<int32_t> list;
+    std::vector<FsObs> obs_host;
+    std::vector<int64_t> run_off;          // loaded run: record offsets per step, [steps + 1]
+    hipEvent_t ev[4][2] = {};
+    bool ran[4] = {false, false, false, false};
+};
+
+namespace {
+
+// One step's observation list against the argument rules (host only)
+int fs_check_list(int32_t nl, const char* who, int32_t k, const int64_t* ids, const double* obs) {
+    if (k < 0 || k > nl) return fail(SLAM_ERR_ARG, std::string(who) + ": need 0 <= k <= n_landmarks");
+    if (k > 0 && (!ids || !obs)) return fail(SLAM_ERR_ARG, std::string(who) + ": NULL ids / obs");
+    for (int32_t t = 0; t < k; ++t) {
+        if (ids[t] < 0 || ids[t] >= nl)
+            return fail(SLAM_ERR_ARG, std::string(who) + ": landmark id out of range");
+        const double d = obs[3 * t], phi = obs[3 * t + 1], psi = obs[3 * t + 2];
+        if (!(std::isfinite(d) && std::isfinite(phi) && std::isfinite(psi)))
+            return fail(SLAM_ERR_ARG, std::string(who) + ": non-finite observation");
+        if (!(d > 0.0)) return fail(SLAM_ERR_ARG, std::string(who) + ": observed range d <= 0");
+    }
+    std::vector<int64_t> s(ids, ids + k);
+    std::sort(s.begin(), s.end());
+    if (std::adjacent_find(s.begin(), s.end()) != s.end())
+        return fail(SLAM_ERR_ARG, std::string(who) + ": duplicate landmark id within one step");
+    return SLAM_OK;
+}
+
+int fs_check_obs(slam_fs* f, const char* who, int32_t k, const int64_t* ids, const double* obs) {
+    return fs_check_list(f->nl, who, k, ids, obs);
+}
+
+// the particle-independent terms of one observation (scan_cov with the observed range)
+FsObs fs_make_obs(const slam_fs* f, int64_t id, const double* o) {
+    FsObs r;
+    r.d = o[0];
+    r.phi = o[1];
+    r.psi = o[2];
+    const double a = r.d * f->cfg.r_dist, b = r.d * std::sin(f->cfg.r_dir);
+    r.r0 = a * a;
+    r.r1 = b * b;
+    r.rx = r.d * std::cos(r.phi);
+    r.ry = r.d * std::sin(r.phi);
+    r.vo = f->cfg.r_dir * f->cfg.r_dir + f->cfg.r_orient * f->cfg.r_orient;
+    r.id = id;
+    return r;
+}
+
+int fs_reserve_obs(slam_fs* f, int64_t count) {
+    if (count <= f->obs_cap) return SLAM_OK;
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    if (f->obs_dev) (void)hipFree(f->obs_dev);
+    f->obs_dev = nullptr;
+    f->obs_cap = 0;
+    SLAM_HIP_TRY(hipMalloc((void**)&f->obs_dev, sizeof(FsObs) * (size_t)count));
+    f->obs_cap = count;
+    return SLAM_OK;
+}
+
+int fs_reserve_stage(slam_fs* f, int64_t doubles) {
+    if (doubles <= f->stage_cap) return SLAM_OK;
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    if (f->stage) (void)hipFree(f->stage);
+    f->stage = nullptr;
+    f->stage_cap = 0;
+    SLAM_HIP_TRY(hipMalloc((void**)&f->stage, sizeof(double) * (size_t)doubles));
+    f->stage_cap = doubles;
+    return SLAM_OK;
+}
+
+void fs_tic(slam_fs* f, int k) {
+    (void)hipEventRecord(f->ev[k][0], f->pf->stream);
+    f->ran[k] = true;
+}
+void fs_toc(slam_fs* f, int k) { (void)hipEventRecord(f->ev[k][1], f->pf->stream); }
+
+inline dim3 fs_grid(int64_t n, int64_t rows) {
+    return dim3(grid_for(n, kFsThreads), (unsigned)std::max<int64_t>(1, std::min<int64_t>(rows, 65535)));
+}
+
+// __resampling (particle_filter.py:200-224) as slam_pf_resample enqueues it,
+// then the maps of the seen landmarks through the same indices.  The clamp's
+// status bit stays in the flags: the step end's record carries it (a
+// stand-alone slam_fs_resample reads and clears it itself).
+int fs_enqueue_resample(slam_fs* f, double u) {
+    slam_pf* h = f->pf;
+    int rc = stage_scan_offset(h, u);
+    if (rc || (rc = launch_scans(h, 1, true)) || (rc = retire_scan_marks(h))) return rc;
+    const double ofs = std::isnan(u) ? u : u * h->pc.np_recip;
+    resample_search_kernel<<<grid_for(h->n, 256), 256, 0, h->stream>>>(
+        h->n, h->c, h->idx, h->pc.rstep, ofs, h->pc.np_recip, h->cfg.seed, h->stepno, h->flags);
+    const int src = h->cur, dst = 1 - h->cur;
+    gather_kernel<<<grid_for(h->n, 256), 256, 0, h->stream>>>(
+        h->n, h->idx, h->x[src], h->y[src], h->th[src], h->x[dst], h->y[dst], h->th[dst], h->w_un,
+        h->pc.np_recip);
+    SLAM_HIP_TRY(hipGetLastError());
+    if ((rc = set_s_one(h))) return rc;
+    h->cur = dst;
+    f->list.clear();
+    for (int32_t j = 0; j < f->nl; ++j)
+        if (f->seen[(size_t)j]) f->list.push_back(j);
+    fs_tic(f, 0);
+    if (!f->list.empty()) {
+        SLAM_HIP_TRY(hipMemcpyAsync(f->list_dev, f->list.data(), f->list.size() * sizeof(int32_t),
+                                    hipMemcpyHostToDevice, h->stream));
+        fs_map_gather_kernel<<<fs_grid(f->n, (int64_t)f->list.size()), kFsThreads, 0, h->stream>>>(
+            f->n, f->npad, h->idx, f->list_dev, (int32_t)f->list.size(), f->map[f->mcur],
+            f->map[1 - f->mcur]);
+        SLAM_HIP_TRY(hipGetLastError());
+        f->mcur = 1 - f->mcur;
+    }
+    fs_toc(f, 0);
+    h->resample_next = 0;
+    return set_flag(h, kFlagResample, 0);
+}
+
+// __predict (particle_filter.py:156-168): the single handle's fused launch
+// with zero landmarks -- the weights pass through (w_un = w, s = 1)
+int fs_enqueue_predict(slam_fs* f, const double* control, const double* noise) {
+    slam_pf* h = f->pf;
+    int rc;
+    if ((rc = stage_inputs(h, control, nullptr, noise, std::nan("")))) return rc;
+    if ((rc = set_flag(h, kFlagResample, 0))) return rc;
+    fs_tic(f, 1);
+    rc = launch_fused(h, h->cfg.motion, noise != nullptr);
+    fs_toc(f, 1);
+    if (rc || (rc = set_s_one(h))) return rc;
+    h->stepno++;
+    return SLAM_OK;
+}
+
+// the per-particle map update with its log weights, the weights, then the
+// single handle's step end on the current particles (its update stage with
+// zero landmarks: the block partials of the new w_un, then the finalize)
+int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled) {
+    slam_pf* h = f->pf;
+    int rc;
+    fs_tic(f, 2);
+    if (k > 0) {
+        const int c = h->cur;
+        fs_update_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(
+            f->n, f->npad, h->x[c], h->y[c], h->th[c], f->map[f->mcur], k, obs, f->seen_dev,
+            f->cfg.use_orient, f->L, f->bmax);
+        fs_max_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->nb, f->bmax + f->nb);
+        fs_weight_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(f->n, f->L, f->bmax + f->nb, h->w_un);
+        fs_mark_seen_kernel<<<grid_for(k, kFsThreads), kFsThreads, 0, h->stream>>>(k, obs, f->seen_dev);
+        SLAM_HIP_TRY(hipGetLastError());
+    }
+    fs_toc(f, 2);
+    static const double ctl0[2] = {0.0, 0.0};
+    SLAM_HIP_TRY(hipMemcpyAsync(h->ctl, ctl0, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if ((rc = set_ctr(h, 0)) || (rc = set_flag(h, kFlagResample, 0))) return rc;
+    fs_tic(f, 3);
+    if ((rc = launch_fused(h, kMotionNone, false)) || (rc = launch_reduce(h, resampled))) return rc;
+    fs_toc(f, 3);
+    return SLAM_OK;
+}
+
+void fs_note_seen(slam_fs* f, int32_t k, const FsObs* obs) {
+    for (int32_t t = 0; t < k; ++t) f->seen[(size_t)obs[t].id] = 1;
+}
+
+// one whole step from k records already on the device (host copies in host_obs)
+int fs_step_records(slam_fs* f, const double* control, int32_t k, const FsObs* dev_obs,
+                    const FsObs* host_obs, const double* noise, double u, slam_pf_result* res) {
+    slam_pf* h = f->pf;
+    h->prep_step = -1;
+    for (int q = 0; q < 4; ++q) f->ran[q] = false;
+    const int32_t resampling = h->resample_next;
+    int rc;
+    if (resampling && (rc = fs_enqueue_resample(f, u))) return rc;
+    if ((rc = fs_enqueue_predict(f, control, noise))) return rc;
+    if ((rc = fs_enqueue_update(f, k, dev_obs, resampling))) return rc;
+    fs_note_seen(f, k, host_obs);
+    return sync_results(h, 0, 1, res);      // the step's one host read
+}
+
+int fs_stage_step_obs(slam_fs* f, int32_t k, const int64_t* ids, const double* obs) {
+    f->obs_host.resize((size_t)k);
+    for (int32_t t = 0; t < k; ++t) f->obs_host[(size_t)t] = fs_make_obs(f, ids[t], obs + 3 * t);
+    f->run_off.clear();                     // the device records no longer hold a loaded run
+    if (k == 0) return SLAM_OK;
+    int rc = fs_reserve_obs(f, k);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipMemcpyAsync(f->obs_dev, f->obs_host.data(), sizeof(FsObs) * (size_t)k,
+                                hipMemcpyHostToDevice, f->pf->stream));
+    return SLAM_OK;
+}
+
+// maps between the host layout and the device's, a slab of particles at a time
+constexpr int64_t kFsStageDoubles = int64_t(1) << 22;      // 32 MiB
+
+int fs_maps_io(slam_fs* f, bool to_device, double* mean, double* cov) {
+    slam_pf* h = f->pf;
+    const int64_t per = 3 * (int64_t)f->nl;
+    const int64_t slab = std::max<int64_t>(1, std::min<int64_t>(f->n, kFsStageDoubles / per));
+    int rc = fs_reserve_stage(f, slab * per);
+    if (rc) return rc;
+    for (int pass = 0; pass < 2; ++pass) {
+        double* host = pass == 0 ? mean : cov;
+        if (!host) continue;
+        const int32_t comp0 = pass == 0 ? 0 : 2, ncomp = pass == 0 ? 2 : 3;
+        for (int64_t p0 = 0; p0 < f->n; p0 += slab) {
+            const int64_t cnt = std::min<int64_t>(slab, f->n - p0);
+            const size_t bytes = sizeof(double) * (size_t)cnt * f->nl * ncomp;
+            double* hp = host + (size_t)p0 * f->nl * ncomp;
+            if (to_device) {
+                SLAM_HIP_TRY(hipMemcpyAsync(f->stage, hp, bytes, hipMemcpyHostToDevice, h->stream));
+                // the slab's particles are rows p0.. of the staged array
+                fs_map_unpack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
+                    cnt, f->npad, f->nl, comp0, ncomp, f->stage, f->map[f->mcur] + p0);
+            } else {
+                fs_map_pack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
+                    f->n, f->npad, f->nl, p0, cnt, comp0, ncomp, f->seen_dev, f->map[f->mcur],
+                    f->stage);
+                SLAM_HIP_TRY(hipMemcpyAsync(hp, f->stage, bytes, hipMemcpyDeviceToHost, h->stream));
+            }
+            SLAM_HIP_TRY(hipGetLastError());
+            SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+    }
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_fs_check_observations(int32_t n_landmarks, int32_t k, const int64_t* ids, const double* obs) {
+    SLAM_ARG_CHECK(n_landmarks >= 1, "slam_fs_check_observations: need n_landmarks >= 1");
+    return fs_check_list(n_landmarks, "slam_fs_check_observations", k, ids, obs);
+}
+
+int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_landmarks, int device,
+                   slam_fs** out) {
+    SLAM_ARG_CHECK(cfg && out, "slam_fs_create: NULL argument");
+    *out = nullptr;
+    SLAM_ARG_CHECK(n_particles >= 1 && n_particles <= (int64_t(1) << 24),
+                   "slam_fs_create: need 1 <= n_particles <= 2^24");
+    SLAM_ARG_CHECK(n_landmarks >= 1, "slam_fs_create: need n_landmarks >= 1");
+    SLAM_ARG_CHECK(cfg->pf.motion == SLAM_MOTION_LINEAR || cfg->pf.motion == SLAM_MOTION_VELOCITY,
+                   "slam_fs_create: bad motion model");
+    SLAM_ARG_CHECK(cfg->r_dist > 0.0 && std::sin(cfg->r_dir) != 0.0 && std::isfinite(cfg->r_orient),
+                   "slam_fs_create: need r_dist > 0, sin(r_dir) != 0, finite r_orient");
+    slam_pf_config pc = cfg->pf;
+    pc.r_cov[0] = pc.r_cov[3] = 1.0;        // ignored here: the single handle only checks it
+    pc.r_cov[1] = pc.r_cov[2] = 0.0;
+    pc.likelihood = SLAM_LIK_PRODUCT;       // zero landmarks: the factor is exactly 1
+    slam_pf* pf = nullptr;
+    int rc = create_impl(&pc, n_particles, n_particles, 0, 0, nullptr, device, &pf, true, false);
+    if (rc) return rc;
+    slam_fs* f = new slam_fs();
+    f->cfg = *cfg;
+    f->cfg.use_orient = cfg->use_orient ? 1 : 0;
+    f->pf = pf;
+    f->n = n_particles;
+    f->npad = (n_particles + kFsThreads - 1) / kFsThreads * kFsThreads;
+    f->nl = n_landmarks;
+    f->nb = (int32_t)(f->npad / kFsThreads);
+    f->seen.assign((size_t)n_landmarks, 0);
+    const size_t map_bytes = sizeof(double) * (size_t)kFsComp * (size_t)n_landmarks * (size_t)f->npad;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipMalloc((void**)&f->map[k], map_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(f->map[k], 0, map_bytes, pf->stream);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&f->L, sizeof(double) * (size_t)f->npad);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->bmax, sizeof(double) * ((size_t)f->nb + 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->seen_dev, sizeof(int32_t) * (size_t)n_landmarks);
+    if (e == hipSuccess) e = hipMalloc((void**)&f->list_dev, sizeof(int32_t) * (size_t)n_landmarks);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(f->seen_dev, 0, sizeof(int32_t) * (size_t)n_landmarks, pf->stream);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        for (int q = 0; q < 2 && e == hipSuccess; ++q) e = hipEventCreate(&f->ev[k][q]);
+    if (e == hipSuccess) e = hipStreamSynchronize(pf->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        slam_fs_destroy(f);
+        return fail(SLAM_ERR_HIP, std::string("slam_fs_create: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return SLAM_OK;
+}
+
+int slam_fs_destroy(slam_fs* f) {
+    if (!f) return SLAM_OK;
+    if (f->pf) {
+        (void)hipSetDevice(f->pf->device);
+        (void)hipStreamSynchronize(f->pf->stream);
+    }
+    for (int k = 0; k < 2; ++k)
+        if (f->map[k]) (void)hipFree(f->map[k]);
+    if (f->L) (void)hipFree(f->L);
+    if (f->bmax) (void)hipFree(f->bmax);
+    if (f->seen_dev) (void)hipFree(f->seen_dev);
+    if (f->list_dev) (void)hipFree(f->list_dev);
+    if (f->obs_dev) (void)hipFree(f->obs_dev);
+    if (f->stage) (void)hipFree(f->stage);
+    for (auto& pr : f->ev)
+        for (auto& ev : pr)
+            if (ev) (void)hipEventDestroy(ev);
+    slam_pf_destroy(f->pf);
+    delete f;
+    return SLAM_OK;
+}
+
+int slam_fs_info(slam_fs* f, int64_t* n_particles, int32_t* n_landmarks, int32_t* n_seen) {
+    SLAM_ARG_CHECK(f, "slam_fs_info: NULL handle");
+    if (n_particles) *n_particles = f->n;
+    if (n_landmarks) *n_landmarks = f->nl;
+    if (n_seen) *n_seen = (int32_t)std::count(f->seen.begin(), f->seen.end(), 1);
+    return SLAM_OK;
+}
+
+int slam_fs_set_state(slam_fs* f, const double* x, const double* y, const double* th,
+                      const double* w) {
+    SLAM_ARG_CHECK(f, "slam_fs_set_state: NULL handle");
+    return slam_pf_set_state(f->pf, x, y, th, w);
+}
+
+int slam_fs_get_state(slam_fs* f, double* x, double* y, double* th, double* w) {
+    SLAM_ARG_CHECK(f, "slam_fs_get_state: NULL handle");
+    return slam_pf_get_state(f->pf, x, y, th, w);
+}
+
+int slam_fs_set_resample_next(slam_fs* f, int32_t on) {
+    SLAM_ARG_CHECK(f, "slam_fs_set_resample_next: NULL handle");
+    return slam_pf_set_resample_next(f->pf, on);
+}
+
+int slam_fs_set_maps(slam_fs* f, const int32_t* seen, const double* mean, const double* cov) {
+    SLAM_ARG_CHECK(f, "slam_fs_set_maps: NULL handle");
+    SLAM_ARG_CHECK(seen && mean && cov, "slam_fs_set_maps: NULL argument");
+    slam_pf* h = f->pf;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    for (int32_t j = 0; j < f->nl; ++j) f->seen[(size_t)j] = seen[j] ? 1 : 0;
+    SLAM_HIP_TRY(hipMemcpyAsync(f->seen_dev, f->seen.data(), sizeof(int32_t) * (size_t)f->nl,
+                                hipMemcpyHostToDevice, h->stream));
+    return fs_maps_io(f, true, const_cast<double*>(mean), const_cast<double*>(cov));
+}
+
+int slam_fs_get_maps(slam_fs* f, int32_t* seen, double* mean, double* cov) {
+    SLAM_ARG_CHECK(f, "slam_fs_get_maps: NULL handle");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    if (seen) std::copy(f->seen.begin(), f->seen.end(), seen);
+    return fs_maps_io(f, false, mean, cov);
+}
+
+int slam_fs_get_map(slam_fs* f, int64_t particle, int32_t* seen, double* mean, double* cov) {
+    SLAM_ARG_CHECK(f, "slam_fs_get_map: NULL handle");
+    SLAM_ARG_CHECK(particle >= 0 && particle < f->n, "slam_fs_get_map: no such particle");
+    slam_pf* h = f->pf;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    if (seen) std::copy(f->seen.begin(), f->seen.end(), seen);
+    int rc = fs_reserve_stage(f, 5 * (int64_t)f->nl);
+    if (rc) return rc;
+    for (int pass = 0; pass < 2; ++pass) {
+        double* host = pass == 0 ? mean : cov;
+        if (!host) continue;
+        const int32_t comp0 = pass == 0 ? 0 : 2, ncomp = pass == 0 ? 2 : 3;
+        double* st = f->stage + (pass == 0 ? 0 : 2 * (size_t)f->nl);
+        fs_map_pack_kernel<<<fs_grid(1, f->nl), kFsThreads, 0, h->stream>>>(
+            f->n, f->npad, f->nl, particle, 1, comp0, ncomp, f->seen_dev, f->map[f->mcur], st);
+        SLAM_HIP_TRY(hipGetLastError());
+        SLAM_HIP_TRY(hipMemcpyAsync(host, st, sizeof(double) * (size_t)f->nl * ncomp,
+                                    hipMemcpyDeviceToHost, h->stream));
+    }
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+int slam_fs_step(slam_fs* f, const double* control, int32_t k, const int64_t* ids, const double* obs,
+                 const double* noise, double u_resample, slam_pf_result* res) {
+    SLAM_ARG_CHECK(f && control, "slam_fs_step: NULL argument");
+    int rc = fs_check_obs(f, "slam_fs_step", k, ids, obs);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    if ((rc = fs_stage_step_obs(f, k, ids, obs))) return rc;
+    return fs_step_records(f, control, k, f->obs_dev, f->obs_host.data(), noise, u_resample, res);
+}
+
+int slam_fs_resample(slam_fs* f, double u_resample, int32_t force, int32_t* resampled) {
+    SLAM_ARG_CHECK(f, "slam_fs_resample: NULL handle");
+    slam_pf* h = f->pf;
+    h->prep_step = -1;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    const int32_t go = force ? 1 : h->resample_next;
+    if (resampled) *resampled = go;
+    if (!go) return SLAM_OK;
+    int rc = fs_enqueue_resample(f, u_resample);
+    if (rc) return rc;
+    int32_t st = 0;
+    SLAM_HIP_TRY(hipMemcpyAsync(&st, h->flags + kFlagStatus, 4, hipMemcpyDeviceToHost, h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = set_flag(h, kFlagStatus, 0))) return rc;
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    if (st & 1)
+        return fail(SLAM_ERR_INDEX, "resample position beyond the last cumulative weight "
+                                    "(IndexError in particle_filter.py:219)");
+    return SLAM_OK;
+}
+
+int slam_fs_predict(slam_fs* f, const double* control, const double* noise) {
+    SLAM_ARG_CHECK(f && control, "slam_fs_predict: NULL argument");
+    slam_pf* h = f->pf;
+    h->prep_step = -1;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    int rc = fs_enqueue_predict(f, control, noise);
+    if (rc || (rc = set_flag(h, kFlagResample, h->resample_next))) return rc;
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+int slam_fs_update(slam_fs* f, int32_t k, const int64_t* ids, const double* obs,
+                   slam_pf_result* res) {
+    SLAM_ARG_CHECK(f, "slam_fs_update: NULL handle");
+    int rc = fs_check_obs(f, "slam_fs_update", k, ids, obs);
+    if (rc) return rc;
+    slam_pf* h = f->pf;
+    h->prep_step = -1;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    if ((rc = fs_stage_step_obs(f, k, ids, obs))) return rc;
+    if ((rc = fs_enqueue_update(f, k, f->obs_dev, 0))) return rc;
+    fs_note_seen(f, k, f->obs_host.data());
+    return sync_results(h, 0, 1, res);
+}
+
+int slam_fs_load_observations(slam_fs* f, int32_t n_steps, const int32_t* counts, const int64_t* ids,
+                              const double* obs) {
+    SLAM_ARG_CHECK(f, "slam_fs_load_observations: NULL handle");
+    SLAM_ARG_CHECK(n_steps > 0 && counts, "slam_fs_load_observations: bad argument");
+    std::vector<int64_t> off((size_t)n_steps + 1, 0);
+    int rc;
+    for (int32_t s = 0; s < n_steps; ++s) {
+        const int64_t o = off[(size_t)s];
+        if ((rc = fs_check_obs(f, "slam_fs_load_observations", counts[s], ids ? ids + o : nullptr,
+                               obs ? obs + 3 * o : nullptr)))
+            return rc;
+        off[(size_t)s + 1] = o + counts[s];
+    }
+    const int64_t total = off[(size_t)n_steps];
+    f->obs_host.resize((size_t)total);
+    for (int64_t t = 0; t < total; ++t) f->obs_host[(size_t)t] = fs_make_obs(f, ids[t], obs + 3 * t);
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    f->run_off.clear();
+    if (total > 0) {
+        if ((rc = fs_reserve_obs(f, total))) return rc;
+        SLAM_HIP_TRY(hipMemcpyAsync(f->obs_dev, f->obs_host.data(), sizeof(FsObs) * (size_t)total,
+                                    hipMemcpyHostToDevice, f->pf->stream));
+        SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    }
+    f->run_off = std::move(off);
+    return SLAM_OK;
+}
+
+int slam_fs_run(slam_fs* f, int32_t first_step, int32_t n_steps, const double* controls,
+                slam_pf_result* results) {
+    SLAM_ARG_CHECK(f && controls && n_steps > 0, "slam_fs_run: bad argument");
+    SLAM_ARG_CHECK(first_step >= 0 && (size_t)first_step + (size_t)n_steps < f->run_off.size(),
+                   "slam_fs_run: steps outside the loaded observations");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    for (int32_t s = 0; s < n_steps; ++s) {
+        const int64_t o = f->run_off[(size_t)(first_step + s)];
+        const int32_t k = (int32_t)(f->run_off[(size_t)(first_step + s) + 1] - o);
+        const int rc = fs_step_records(f, controls + 2 * s, k, f->obs_dev + o, f->obs_host.data() + o,
+                                       nullptr, std::nan(""), results ? results + s : nullptr);
+        if (rc) return rc;
+    }
+    return SLAM_OK;
+}
+
+int slam_fs_timing(slam_fs* f, double* out) {
+    SLAM_ARG_CHECK(f && out, "slam_fs_timing: NULL argument");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        if (f->ran[k]) SLAM_HIP_TRY(hipEventElapsedTime(&ms, f->ev[k][0], f->ev[k][1]));
+        out[k] = ms;
+    }
+    return SLAM_OK;
+}
+
+}  // extern "C"

@@ -1422,3 +1422,5 @@ int slam_pf_timing(slam_pf* h, int32_t kernel, double* total_ms, int64_t* launch
 }
 
 }  // extern "C"
+
+#include "fs_api.inl"

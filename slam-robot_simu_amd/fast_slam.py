@@ -1,0 +1,76 @@
+"""FastSLAM 1.0 with known data association on the MI355X kernels
+(libslam_hip.so): the particle-filter form of SLAM, an extension -- the
+reference's particle filter (particle_filter.py) localises against a known map.
+
+``FastSLAM(n_particles, n_landmarks)`` keeps, per particle, a pose and one 2-D
+EKF per landmark on the GPU (slamhip.fastslam.DeviceFastSLAM).
+``step(control, observations)`` takes what a limited-range sensor saw this
+step -- either ``(ids, obs)`` with ``obs`` rows (range, bearing, orientation),
+or the list of ``Observation`` objects that ``ScanSensor.scan`` returns -- and
+returns the pose estimate, the particle covariance and the best particle's map.
+
+A headless example: a robot on the reference's circle (particle_filter.py:46-48)
+with a scan sensor of 9 m range::
+
+    import numpy as np
+    from fast_slam import FastSLAM
+    from graph_based_slam import ScanSensor
+
+    landmarks = np.random.RandomState(3).uniform(-12, 12, (7, 2))
+    sensor = ScanSensor(9.0, np.deg2rad(180.0), landmarks)
+    slam = FastSLAM(4096, len(landmarks), ess_threshold=2048, seed=1)
+    pose = np.array([10.0, 0.0, np.pi / 2])
+    v, w, dt = 10.0 * np.deg2rad(10.0), np.deg2rad(10.0), 0.1
+    for _ in range(100):
+        pose = pose + np.array([v * dt * np.cos(pose[2]), v * dt * np.sin(pose[2]), w * dt])
+        noisy, _ = sensor.scan(pose)
+        est, cov, (seen, mean, mcov) = slam.step((v, w), noisy)
+    print(est, mean[seen.astype(bool)])
+    slam.close()
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from slamhip.fastslam import DeviceFastSLAM
+
+
+def _split(observations):
+    """(ids, obs) from either form of a step's observations."""
+    if isinstance(observations, tuple) and len(observations) == 2 and \
+            not hasattr(observations[0], "getLandMarkId"):
+        ids, obs = observations
+        return np.asarray(ids, dtype=np.int64).reshape(-1), np.asarray(obs, dtype=np.float64).reshape(-1, 3)
+    obs_list = list(observations)
+    ids = np.array([o.getLandMarkId() for o in obs_list], dtype=np.int64)
+    obs = np.array([[o.getDist(), o.getDir(), o.getOrient()] for o in obs_list],
+                   dtype=np.float64).reshape(-1, 3)
+    return ids, obs
+
+
+class FastSLAM:
+    """Keyword arguments are DeviceFastSLAM's (dt, q, alphas, x0, motion,
+    noise=(r_dist, r_dir, r_orient), use_orient, ess_threshold, seed, device);
+    the measurement noise defaults to ScanSensor's (10 %, 3 deg, 3 deg)."""
+
+    def __init__(self, n_particles, n_landmarks, **kw):
+        self.dev = DeviceFastSLAM(n_particles, n_landmarks, **kw)
+        self.last = None
+
+    def step(self, control, observations, noise=None, u_resample=float("nan")):
+        """One step: returns (x_est (3,), cov (3, 3), (seen, mean [NL][2],
+        cov [NL][3])) -- the heaviest particle's pose and map, and the
+        weighted particle covariance.  The motion noise and the resampling
+        offset come from the device RNG unless given (as slam_pf_step)."""
+        ids, obs = _split(observations)
+        self.last = self.dev.step(control, ids, obs, noise, u_resample)
+        return self.last["x_est"], self.last["cov"], self.dev.best_map()
+
+    def close(self):
+        self.dev.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

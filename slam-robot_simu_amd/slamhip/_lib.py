@@ -52,6 +52,11 @@ class EKFSLAMConfig(C.Structure):
                 ("pad0", C.c_int32), ("alphas", C.c_double * 6)]
 
 
+class FSConfig(C.Structure):
+    _fields_ = [("pf", PFConfig), ("r_dist", C.c_double), ("r_dir", C.c_double),
+                ("r_orient", C.c_double), ("use_orient", C.c_int32), ("pad0", C.c_int32)]
+
+
 class GraphEdge(C.Structure):
     _fields_ = [("time_bfr", C.c_int64), ("pose_bfr", C.c_int64), ("time_aft", C.c_int64),
                 ("pose_aft", C.c_int64), ("obs_bfr", C.c_double * 3), ("obs_aft", C.c_double * 3)]
@@ -176,6 +181,23 @@ SIGNATURES = {
     "slam_ekfslam_update": (C.c_int, [_P, C.c_int32, _I64, _D]),
     "slam_ekfslam_step": (C.c_int, [_P, _D, C.c_int32, _I64, _D]),
     "slam_ekfslam_timing": (C.c_int, [_P, _D]),
+    "slam_fs_check_observations": (C.c_int, [C.c_int32, C.c_int32, _I64, _D]),
+    "slam_fs_create": (C.c_int, [C.POINTER(FSConfig), C.c_int64, C.c_int32, C.c_int, C.POINTER(_P)]),
+    "slam_fs_destroy": (C.c_int, [_P]),
+    "slam_fs_info": (C.c_int, [_P, _I64, _I32, _I32]),
+    "slam_fs_set_state": (C.c_int, [_P, _D, _D, _D, _D]),
+    "slam_fs_get_state": (C.c_int, [_P, _D, _D, _D, _D]),
+    "slam_fs_set_resample_next": (C.c_int, [_P, C.c_int32]),
+    "slam_fs_set_maps": (C.c_int, [_P, _I32, _D, _D]),
+    "slam_fs_get_maps": (C.c_int, [_P, _I32, _D, _D]),
+    "slam_fs_get_map": (C.c_int, [_P, C.c_int64, _I32, _D, _D]),
+    "slam_fs_step": (C.c_int, [_P, _D, C.c_int32, _I64, _D, _D, C.c_double, C.POINTER(PFResult)]),
+    "slam_fs_resample": (C.c_int, [_P, C.c_double, C.c_int32, _I32]),
+    "slam_fs_predict": (C.c_int, [_P, _D, _D]),
+    "slam_fs_update": (C.c_int, [_P, C.c_int32, _I64, _D, C.POINTER(PFResult)]),
+    "slam_fs_load_observations": (C.c_int, [_P, C.c_int32, _I32, _I64, _D]),
+    "slam_fs_run": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.POINTER(PFResult)]),
+    "slam_fs_timing": (C.c_int, [_P, _D]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

@@ -1,0 +1,220 @@
+"""Device FastSLAM 1.0 (known data association): a handle on libslam_hip's
+slam_fs_* entry points.
+
+Every particle carries a pose, a weight and one 2-D EKF (mean, symmetric 2 x 2
+covariance) per landmark, resident in HBM; a step observes any subset of the
+landmarks as (range, bearing, orientation) triples with their ids -- what
+``ScanSensor.scan`` returns.  Resampling, prediction and the step end are the
+single particle filter's (slamhip.pf); the per-particle map update with its
+log-domain weights and the resampling gather of whole maps are this handle's
+own kernels (csrc/fastslam.inl).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import FSConfig, PFResult, check, dptr
+from .pf import DeviceParticleFilter, RunResults, _f64, make_config
+
+
+def _ids_obs(ids, obs):
+    ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 3)
+    if obs.shape[0] != ids.size:
+        raise ValueError("ids and obs disagree in length")
+    return ids, obs
+
+
+class DeviceFastSLAM:
+    """Particles with per-particle landmark maps on one GPU.
+
+    ``noise`` = (r_dist, r_dir, r_orient): ScanSensor's range noise fraction and
+    its bearing / orientation sigmas (rad).  The other keywords are
+    DeviceParticleFilter's."""
+
+    ESS_CONFIRM_BAND = DeviceParticleFilter.ESS_CONFIRM_BAND
+
+    def __init__(self, n_particles, n_landmarks, *, dt=0.1, q=None, alphas=(0.1,) * 6,
+                 x0=(10.0, 0.0, np.pi / 2), motion="linear",
+                 noise=(0.1, np.deg2rad(3.0), np.deg2rad(3.0)), use_orient=True,
+                 ess_threshold=None, seed=0, device=0):
+        lib = _lib.load()
+        self.n = int(n_particles)
+        self.nl = int(n_landmarks)
+        cfg = FSConfig()
+        cfg.pf = make_config(self.n, dt=dt, q=q, x0=x0, motion=motion, alphas=alphas,
+                             ess_threshold=ess_threshold, seed=seed)
+        cfg.r_dist, cfg.r_dir, cfg.r_orient = (float(v) for v in noise)
+        cfg.use_orient = int(bool(use_orient))
+        self.cfg = cfg
+        self.motion = motion
+        h = C.c_void_p()
+        check(lib.slam_fs_create(C.byref(cfg), self.n, self.nl, int(device), C.byref(h)),
+              "slam_fs_create")
+        self._h = h
+        self._lib = lib
+        self.resample_next = False
+        self.last = None
+        self._run_steps = 0
+
+    # ------------------------------------------------------------ lifetime
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.slam_fs_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    # --------------------------------------------------------------- state
+    def info(self):
+        n, nl, ns = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        check(self._lib.slam_fs_info(self._h, C.byref(n), C.byref(nl), C.byref(ns)), "slam_fs_info")
+        return dict(n_particles=n.value, n_landmarks=nl.value, n_seen=ns.value)
+
+    def set_state(self, x=None, y=None, th=None, w=None):
+        arrs = [None if a is None else _f64(a, (self.n,)) for a in (x, y, th, w)]
+        check(self._lib.slam_fs_set_state(self._h, *[dptr(a) for a in arrs]), "slam_fs_set_state")
+        if w is not None:
+            ww = arrs[3]
+            self.set_resample_next(bool(1.0 / float(ww @ ww) < self.cfg.pf.ess_threshold))
+
+    def get_state(self):
+        out = [np.empty(self.n) for _ in range(4)]
+        check(self._lib.slam_fs_get_state(self._h, *[dptr(a) for a in out]), "slam_fs_get_state")
+        return tuple(out)
+
+    def set_resample_next(self, on):
+        check(self._lib.slam_fs_set_resample_next(self._h, int(bool(on))),
+              "slam_fs_set_resample_next")
+        self.resample_next = bool(on)
+
+    def set_maps(self, seen, mean, cov):
+        """seen [NL], mean [NP][NL][2], cov [NP][NL][3] (pxx, pxy, pyy)."""
+        seen = np.ascontiguousarray(seen, dtype=np.int32).reshape(self.nl)
+        mean = _f64(mean, (self.n, self.nl, 2))
+        cov = _f64(cov, (self.n, self.nl, 3))
+        check(self._lib.slam_fs_set_maps(self._h, seen.ctypes.data_as(_lib._I32), dptr(mean),
+                                         dptr(cov)), "slam_fs_set_maps")
+
+    def get_maps(self):
+        """(seen, mean, cov) of every particle; unseen landmarks are NaN."""
+        seen = np.empty(self.nl, dtype=np.int32)
+        mean = np.empty((self.n, self.nl, 2))
+        cov = np.empty((self.n, self.nl, 3))
+        check(self._lib.slam_fs_get_maps(self._h, seen.ctypes.data_as(_lib._I32), dptr(mean),
+                                         dptr(cov)), "slam_fs_get_maps")
+        return seen, mean, cov
+
+    def get_map(self, particle):
+        """(seen, mean [NL][2], cov [NL][3]) of one particle, O(NL)."""
+        seen = np.empty(self.nl, dtype=np.int32)
+        mean = np.empty((self.nl, 2))
+        cov = np.empty((self.nl, 3))
+        check(self._lib.slam_fs_get_map(self._h, int(particle), seen.ctypes.data_as(_lib._I32),
+                                        dptr(mean), dptr(cov)), "slam_fs_get_map")
+        return seen, mean, cov
+
+    def best_map(self):
+        """The map estimate: the map of the last step's heaviest particle, as
+        x_est is its pose."""
+        if self.last is None:
+            raise RuntimeError("best_map: no step has run yet")
+        return self.get_map(self.last["max_idx"])
+
+    # ---------------------------------------------------------------- step
+    def _confirm_ess(self, out):
+        """DeviceParticleFilter._confirm_ess: an ess_near step's resample
+        decision re-formed on the host by the reference's own expression."""
+        th = self.cfg.pf.ess_threshold
+        out["ess_confirmed"] = False
+        if not abs(out["ess"] - th) <= self.ESS_CONFIRM_BAND * th:
+            return out
+        pw = self.get_state()[3]
+        ess = float(np.reciprocal(pw @ pw.T))
+        rn = ess < th
+        if rn != bool(out["resample_next"]):
+            self.set_resample_next(rn)
+        out.update(resample_next=rn, ess_host=ess, ess_confirmed=True)
+        self.resample_next = rn
+        return out
+
+    def _finish(self, res):
+        out = DeviceParticleFilter._res(res)
+        self.resample_next = out["resample_next"]
+        self._confirm_ess(out)
+        self.last = out
+        return out
+
+    def step(self, control, ids, obs, noise=None, u_resample=float("nan")):
+        ctl = _f64(control, (2,))
+        ids, obs = _ids_obs(ids, obs)
+        nz = None if noise is None else _f64(noise, (self.n, 3))
+        res = PFResult()
+        check(self._lib.slam_fs_step(self._h, dptr(ctl), ids.size, ids.ctypes.data_as(_lib._I64),
+                                     dptr(obs), dptr(nz), float(u_resample), C.byref(res)),
+              "slam_fs_step")
+        return self._finish(res)
+
+    def resample(self, u_resample=float("nan"), force=False):
+        flag = C.c_int32(0)
+        check(self._lib.slam_fs_resample(self._h, float(u_resample), int(bool(force)),
+                                         C.byref(flag)), "slam_fs_resample")
+        if flag.value:
+            self.resample_next = False
+        return bool(flag.value)
+
+    def predict(self, control, noise=None):
+        ctl = _f64(control, (2,))
+        nz = None if noise is None else _f64(noise, (self.n, 3))
+        check(self._lib.slam_fs_predict(self._h, dptr(ctl), dptr(nz)), "slam_fs_predict")
+
+    def update(self, ids, obs):
+        ids, obs = _ids_obs(ids, obs)
+        res = PFResult()
+        check(self._lib.slam_fs_update(self._h, ids.size, ids.ctypes.data_as(_lib._I64), dptr(obs),
+                                       C.byref(res)), "slam_fs_update")
+        return self._finish(res)
+
+    # ------------------------------------------------------- multi-step run
+    def load_observations(self, steps):
+        """steps: a sequence of (ids, obs) per step, uploaded once."""
+        pairs = [_ids_obs(i, o) for i, o in steps]
+        counts = np.array([i.size for i, _ in pairs], dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate([i for i, _ in pairs] + [np.zeros(0, np.int64)]))
+        obs = np.ascontiguousarray(np.concatenate([o for _, o in pairs] + [np.zeros((0, 3))]))
+        check(self._lib.slam_fs_load_observations(self._h, len(pairs),
+                                                  counts.ctypes.data_as(_lib._I32),
+                                                  ids.ctypes.data_as(_lib._I64), dptr(obs)),
+              "slam_fs_load_observations")
+        self._run_steps = len(pairs)
+
+    def run(self, first_step, controls):
+        """Steps [first_step, first_step + len(controls)) of the loaded
+        observations with the device RNG; the records of ``step`` in turn."""
+        controls = _f64(controls).reshape(-1, 2)
+        k = controls.shape[0]
+        res = (PFResult * k)()
+        check(self._lib.slam_fs_run(self._h, int(first_step), k, dptr(controls), res), "slam_fs_run")
+        self.resample_next = bool(res[k - 1].resample_next)
+        self.last = DeviceParticleFilter._res(res[k - 1])
+        return RunResults(res)
+
+    def timing(self):
+        """HIP-event ms of the last step's {map gather, predict, map update +
+        weights, step end}."""
+        out = np.zeros(4)
+        check(self._lib.slam_fs_timing(self._h, dptr(out)), "slam_fs_timing")
+        return dict(zip(("map_gather", "predict", "map_update", "step_end"), out.tolist()))
