@@ -75,6 +75,11 @@ struct slam_pf {
     SpecialIn* spec_in = nullptr;
     SpecialIn* stage = nullptr;     // lean exact cumsum: per-tile staged specials
     SpecialOut* spec_out = nullptr;
+    // merged exact-cumsum launch: hand-off records and the folded specials,
+    // both as tagged granules (pf_kernels.hpp); zero at creation, which no
+    // epoch equals (the token word starts at 0, the first epoch is 1)
+    uint64_t* hand = nullptr;
+    uint64_t* spec_tag = nullptr;
     // reductions
     int32_t nchunks = 0;
     double* part = nullptr;
@@ -322,7 +327,8 @@ int launch_scans(slam_pf* h, int32_t force, bool with_s1) {
         scan_lean_merged_kernel<<<nb, kScanThreads, 0, s>>>(
             h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->stage, h->bk, h->bf, h->boffk,
             h->bofff, h->ktot, h->nspec, tk, h->flags, force, h->spec_out, h->c, step_io(h), h->pc,
-            h->cfg.seed, h->dp.mark, h->dp.carry, h->flags + kFlagScanToken, h->nb_part);
+            h->cfg.seed, h->dp.mark, h->dp.carry, h->flags + kFlagScanToken, h->hand, h->spec_tag,
+            h->nb_part);
         SLAM_HIP_TRY(hipGetLastError());
         return SLAM_OK;
     }
@@ -786,6 +792,13 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     A(h->spec_in, n);
     if (deferred) A(h->stage, n);
     A(h->spec_out, n);
+    if (h->scan_merged_ok) {
+        A(h->hand, (size_t)(h->nb_scan + kHandReplicas) * kHandGranules);
+        A(h->spec_tag, (size_t)n * kSpecGranules);
+        SLAM_HIP_TRY(hipMemsetAsync(h->hand, 0, sizeof(uint64_t) * (h->nb_scan + kHandReplicas) * kHandGranules,
+                                    h->stream));
+        SLAM_HIP_TRY(hipMemsetAsync(h->spec_tag, 0, sizeof(uint64_t) * n * kSpecGranules, h->stream));
+    }
     A(h->part, h->nchunks);
     A(h->bp, h->nb_norm);
     A(h->wsum, 1);

@@ -212,6 +212,59 @@ __device__ __forceinline__ S ld_wt_struct(const S* p) {
     return v;
 }
 
+// ---- tagged granules (pf_kernels.hpp, the merged exact-cumsum hand-off): a
+// granule validates itself, so neither side fences and nothing relies on the
+// order in which granules become visible.
+__device__ __forceinline__ void st_granule(uint64_t* p, const uint32_t payload, const uint32_t epoch) {
+    st_wt(p, ((uint64_t)epoch << 32) | payload);
+}
+// A block's global offsets into its hand-off record: the two k granules in
+// one 16-byte write-through store (each 8-byte half validates itself, so a
+// store torn between them is harmless), the f granule in another -- a lane's
+// write-through store is one fabric write whatever its size, and the last
+// block issues every block's.
+__device__ __forceinline__ void st_offsets_tagged(uint64_t* rec, const uint64_t k, const int32_t f,
+                                                  const uint32_t epoch) {
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t v = {(uint32_t)k, epoch, (uint32_t)(k >> 32), epoch};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(rec + kHandK0), "v"(v) : "memory");
+    st_granule(rec + kHandF, (uint32_t)f, epoch);
+}
+// A folded special as kSpecGranules tagged granules
+__device__ __forceinline__ void st_spec_tagged(uint64_t* tag, const int64_t m, const SpecialOut& o,
+                                               const uint32_t epoch) {
+    uint64_t* p = tag + m * kSpecGranules;
+    const uint64_t cs = (uint64_t)__double_as_longlong(o.cs);
+    st_granule(p + 0, (uint32_t)cs, epoch);
+    st_granule(p + 1, (uint32_t)(cs >> 32), epoch);
+    st_granule(p + 2, (uint32_t)o.P, epoch);
+    st_granule(p + 3, (uint32_t)(o.P >> 32), epoch);
+    st_granule(p + 4, (uint32_t)o.E, epoch);
+}
+// ... polled until every tag is this launch's epoch (bounded: `lost` if not)
+__device__ __forceinline__ SpecialOut ld_spec_tagged(const uint64_t* tag, const int64_t m,
+                                                     const uint32_t epoch, bool& lost) {
+    const uint64_t* p = tag + m * kSpecGranules;
+    SpecialOut o{};
+    for (int it = 0; it < kHandSpin; ++it) {
+        uint64_t g[kSpecGranules];
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < kSpecGranules; ++k) g[k] = ld_wt(p + k);
+#pragma unroll
+        for (int k = 0; k < kSpecGranules; ++k) ok = ok && (uint32_t)(g[k] >> 32) == epoch;
+        if (ok) {
+            o.cs = __longlong_as_double((long long)((g[1] << 32) | (uint32_t)g[0]));
+            o.P = (g[3] << 32) | (uint32_t)g[2];
+            o.E = (int32_t)(uint32_t)g[4];
+            return o;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    lost = true;
+    return o;
+}
+
 // ---- last-arriver election (Guideline 16 / microarch "fanin" + "dequeue"):
 // every block takes a ticket after publishing its write-through partials.
 // One counter word serialises its arrivals (~12 ns each), so the tickets are

@@ -459,6 +459,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
     __shared__ double s_s;
     __shared__ unsigned long long s_min;
     __shared__ int32_t s_flag;
+    __shared__ int32_t s_next;      // resample_next: a word of its own (a wave still at
+                                    // the tie decision's s_flag must not read it)
     __shared__ int64_t s_mi;
     __shared__ double s_xe[3];
     __shared__ int s_ncand;
@@ -790,7 +792,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
     FIN_STAMP(3);
     if (tid == 0) {
         const int32_t st = io.ctr[0];
-        s_flag = write_result_xe(tot, s_xe, refp, s, flags, ess_th, io.ess_band, io.res + st,
+        s_next = write_result_xe(tot, s_xe, refp, s, flags, ess_th, io.ess_band, io.res + st,
                                  resampled_known, exp ? io.res_host + st : nullptr);
         io.ctr[0] = st + 1;
         io.ctr[1] = io.ctr[1] + 1;
@@ -803,7 +805,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
         // buffer; this step's record went there from write_result_xe
         for (int32_t k = b_first + tid - 1; k < st_now; k += 63) io.res_host[k] = io.res[k];
     }
-    if (s_flag) {
+    if (s_next) {
         double q0[kFinRegBlocks];
 #pragma unroll
         for (int k = 0; k < kFinRegBlocks; ++k) q0[k] = q[k][0];
@@ -851,6 +853,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     __shared__ double s_s;
     __shared__ unsigned long long s_min;
     __shared__ int32_t s_flag;
+    __shared__ int32_t s_next;      // resample_next: a word of its own (a wave still at
+                                    // the tie decision's s_flag must not read it)
     __shared__ int64_t s_mi;
     __shared__ double s_xe[3];
     __shared__ int s_ncand;
@@ -1201,7 +1205,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         s_exp[0] = exp ? 1 : 0;
         s_exp[1] = b_first;
         s_exp[2] = st_now;
-        s_flag = write_result_fw(tot, s_xe, refp, rp, s, flags, fw, ess_th, io.ess_band,
+        s_next = write_result_fw(tot, s_xe, refp, rp, s, flags, fw, ess_th, io.ess_band,
                                  io.res + st_now, resampled_known, exp ? io.res_host + st_now : nullptr);
         io.ctr[0] = st_now + 1;
         io.ctr[1] = rstep + 1;
@@ -1214,7 +1218,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         // buffer; this step's record went there from write_result_fw
         for (int32_t k = s_exp[1] + tid - 1; k < s_exp[2]; k += 63) io.res_host[k] = io.res[k];
     }
-    if (s_flag) {
+    if (s_next) {
         double q0[kFinRegBlocks];
 #pragma unroll
         for (int k = 0; k < kFinRegBlocks; ++k) q0[k] = q[k][0];

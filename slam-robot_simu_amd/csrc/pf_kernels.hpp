@@ -143,6 +143,33 @@ struct SpecialOut {
     int32_t pad;
 };
 
+// Hand-off of the merged exact-cumsum launch: everything its last
+// block hands to the waiting blocks travels as naturally aligned 8-byte
+// granules {payload (low word), epoch tag (high word)}, each written by one
+// write-through store and read by write-through loads until its tag is the
+// launch's epoch.  One record per block on a 128-byte line of its own holds
+// the block's global offsets (written by the tile-total scan, so they travel
+// while the fold runs); the folded specials are kSpecGranules granules each;
+// the fold's verdict is one granule in each of kHandReplicas further lines
+// (block b polls replica b % kHandReplicas: few pollers per word).  A waiting
+// block gathers from these the nine words of HandWord in LDS.
+constexpr int kHandGranules = 16;   // granules per record: one 128-byte line
+constexpr int kHandReplicas = 32;
+enum HandWord {
+    kHandK0 = 0,            // boffk[b], low / high half    (record granules 0, 1)
+    kHandK1 = 1,
+    kHandF = 2,             // bofff[b]                     (record granule 2)
+    kHandCs0 = 3,           // folded special bofff[b] - 1 (0 for the first block): cs halves,
+    kHandCs1 = 4,
+    kHandP0 = 5,            // P halves,
+    kHandP1 = 6,
+    kHandE = 7,             // E
+    kHandFallback = 8,      // the fold fell back to the sequential recurrence
+    kHandUsed = 9,
+};
+constexpr int kSpecGranules = 5;    // cs halves, P halves, E
+constexpr int kHandSpin = 1 << 22;  // bounded wait (polls) before a block gives up
+
 // LikConst of a filter from R (row-major 2x2) and the landmark count; allow_closed:
 // the handle can form the per-step closed-form words (StepIO.zc).
 inline int lik_const_from(const double* R, const int32_t nl, const bool allow_closed, LikConst& lc) {

@@ -490,7 +490,19 @@ __device__ void block_scan_array(const T* in, T* out, const int nb, T* total, T*
 template <int NT, int kC = 8>
 __device__ __forceinline__ void block_scan_pair(const uint64_t* kin, uint64_t* kout, uint64_t* ktotal,
                                 const int32_t* fin, int32_t* fout, int32_t* ftotal, const int nb,
-                                uint64_t* shk, int32_t* shf, int32_t* f_lds = nullptr) {
+                                uint64_t* shk, int32_t* shf, int32_t* f_lds = nullptr,
+                                uint64_t* k_lds = nullptr, const bool lds_only = false) {
+    // lds_only (the merged launch, whose blocks get their offsets from the
+    // hand-off records): no global copy where both LDS copies are kept
+    const bool plain = !(lds_only && f_lds && k_lds);
+    auto put = [&](const int e, const uint64_t kex, const int32_t fex) {
+        if (plain) {
+            st_wt(kout + e, kex);
+            st_wt_i(fout + e, fex);
+        }
+        if (f_lds) f_lds[e] = fex;
+        if (k_lds) k_lds[e] = kex;
+    };
     // Up to two entries per thread: thread-contiguous, in registers, one
     // block scan per array.  Beyond, coalesced: wave w owns the contiguous
     // span [w*span, (w+1)*span) and walks it in rounds of 64 consecutive
@@ -517,9 +529,7 @@ __device__ __forceinline__ void block_scan_pair(const uint64_t* kin, uint64_t* k
 #pragma unroll
         for (int k = 0; k < 2; ++k)
             if (b0 + k < nb) {
-                st_wt(kout + b0 + k, kex);
-                st_wt_i(fout + b0 + k, fex);
-                if (f_lds) f_lds[b0 + k] = fex;
+                put(b0 + k, kex, fex);
                 kex = kex + k2[k];
                 fex = fex + f2[k];
             }
@@ -572,10 +582,7 @@ __device__ __forceinline__ void block_scan_pair(const uint64_t* kin, uint64_t* k
                 const int32_t fi = wave_incl_scan(fv[r]);
                 const int e = e0 + (r0 + r) * 64;
                 if (e < nb) {
-                    const int32_t fex = frun + (fi - fv[r]);
-                    st_wt(kout + e, krun + (ki - kv[r]));
-                    st_wt_i(fout + e, fex);
-                    if (f_lds) f_lds[e] = fex;
+                    put(e, krun + (ki - kv[r]), frun + (fi - fv[r]));
                 }
                 krun += readlane_int(ki, 63);
                 frun += readlane_int(fi, 63);
@@ -1361,28 +1368,56 @@ __device__ __forceinline__ void wave_tile_stage(const int64_t b, const int64_t t
 // two dependent adds per special, operands read from the lanes into SGPRs.
 // Bit-identical to serial_fold; a failed run check takes the same fallback
 // (the plain sequential recurrence, flagged).
+// The merged launch (hand != null in lean_last_block) stores the folded
+// specials as tagged granules instead (tag_out, epoch) and keeps the first
+// kFoldSpecLds of them and the tiles' k offsets in LDS (s_so, s_offk) for the
+// hand-off records.  Returns the failed-run-check verdict to every thread;
+// lean_fold_finish then publishes it and runs the fallback.
 constexpr int kFoldTilesLds = 4096;
-__device__ __forceinline__ void lean_place_fold(const SpecialIn* __restrict__ stage,
+constexpr int kFoldTilesHand = 1024;  // the merged launch (its co-resident grids fit)
+constexpr int kFoldSpecLds = 256;
+__device__ __forceinline__ bool lean_place_fold(const SpecialIn* __restrict__ stage,
                                 const uint64_t* __restrict__ boffk,
                                 const int32_t* __restrict__ bofff, const int ntiles,
                                 const int32_t M, const uint64_t ktot, const int64_t n,
                                 SpecialOut* __restrict__ out, int32_t* __restrict__ flags,
-                                const double* __restrict__ w_un, const double* __restrict__ s_in,
-                                const double np_recip, double* __restrict__ c,
-                                int32_t* __restrict__ s_off) {
-    // s_off: the tiles' special offsets in LDS (kFoldTilesLds words), already
-    // filled by the scan that produced bofff when ntiles fits
+                                int32_t* __restrict__ s_off, const int lds_tiles,
+                                const uint64_t* __restrict__ s_offk = nullptr,
+                                uint64_t* __restrict__ tag_out = nullptr, const uint32_t epoch = 0,
+                                SpecialOut* __restrict__ s_so = nullptr,
+                                uint64_t* __restrict__ hand = nullptr) {
+    // s_off (and s_offk): the tiles' offsets in LDS (lds_tiles words), already
+    // filled by the scan that produced bofff (boffk) when ntiles fits
     __shared__ int s_bad;
-    const bool in_lds = ntiles <= kFoldTilesLds;
+    const bool in_lds = ntiles <= lds_tiles;
+    const bool k_in_lds = s_offk && in_lds;
+    __shared__ int s_issued;
     if (threadIdx.x == 0) {
         s_bad = 0;
+        s_issued = M <= 0;
         flags[kFlagNSpecial] = M;
     }
     __syncthreads();
-    if (threadIdx.x < 64) {
+    if (threadIdx.x >= 64) {
+        // hand (the merged launch): the other waves write every block's offsets
+        // into its hand-off record meanwhile (ntiles is the block count there).
+        // One write-through store per lane is one fabric write, a thousand of
+        // them queue for microseconds in this CU's memory pipeline, and the
+        // fold's own loads would wait behind them: they start once wave 0 has
+        // issued its first chunk's loads, and travel while the chain runs.
+        if (hand) {
+            while (*(volatile int*)&s_issued == 0) __builtin_amdgcn_s_sleep(1);
+            for (int b = threadIdx.x - 64; b < ntiles; b += kScanThreads - 64) {
+                const uint64_t k = k_in_lds ? s_offk[b] : ld_wt(&boffk[b]);
+                const int32_t f = in_lds ? s_off[b] : ld_wt_i(&bofff[b]);
+                st_offsets_tagged(hand + (int64_t)b * kHandGranules, k, f, epoch);
+            }
+        }
+    } else {
         const int lane = threadIdx.x;
-        // special m: its tile (last tile whose offset is <= m), then the staged record
-        auto load_special = [&](const int64_t m, SpecialIn& e) {
+        // special m: its tile (last tile whose offset is <= m), then the staged
+        // record's loads; returns the tile (P is block-local until its offset is added)
+        auto load_special = [&](const int64_t m, SpecialIn& e) -> int {
             int lo = 0, hi = ntiles - 1;
             while (lo < hi) {
                 const int mid = (lo + hi + 1) >> 1;
@@ -1392,7 +1427,7 @@ __device__ __forceinline__ void lean_place_fold(const SpecialIn* __restrict__ st
             }
             const int32_t o = in_lds ? s_off[lo] : ld_wt_i(&bofff[lo]);
             e = ld_wt_struct(&stage[(int64_t)lo * kScanBlock + (m - o)]);
-            e.P += ld_wt(&boffk[lo]);
+            return lo;
         };
         double s = 0.0;
         bool bad = false;
@@ -1400,7 +1435,10 @@ __device__ __forceinline__ void lean_place_fold(const SpecialIn* __restrict__ st
         for (int64_t t0 = 0; t0 < M; t0 += 63) {
             const int64_t m = t0 + lane;
             SpecialIn e{};
-            if (m < M) load_special(m, e);
+            int tile = 0;
+            if (m < M) tile = load_special(m, e);
+            if (t0 == 0 && lane == 0) *(volatile int*)&s_issued = 1;
+            if (m < M) e.P += k_in_lds ? s_offk[tile] : ld_wt(&boffk[tile]);
             // the following special's index and prefix (or the end of the array)
             int64_t nidx = __shfl_down((long long)e.idx, 1, 64);
             uint64_t nP = (uint64_t)__shfl_down((long long)e.P, 1, 64);
@@ -1441,14 +1479,25 @@ __device__ __forceinline__ void lean_place_fold(const SpecialIn* __restrict__ st
                 o.P = e.P;
                 o.E = e.E;
                 o.pad = 0;
-                st_wt_struct(&out[m], o);
+                if (tag_out) st_spec_tagged(tag_out, m, o, epoch);
+                else st_wt_struct(&out[m], o);
+                if (s_so && m < kFoldSpecLds) s_so[m] = o;
             }
         }
         if (__any(bad) && lane == 0) s_bad = 1;
     }
     __syncthreads();
+    return s_bad != 0;
+}
+
+// The fold's verdict for the passes that follow, and the fallback itself
+__device__ __forceinline__ void lean_fold_finish(const bool bad, const int64_t n,
+                                                 int32_t* __restrict__ flags,
+                                                 const double* __restrict__ w_un,
+                                                 const double* __restrict__ s_in,
+                                                 const double np_recip, double* __restrict__ c) {
     if (threadIdx.x == 0) {
-        if (s_bad) {
+        if (bad) {
             flags[kFlagStatus] |= 2;
             st_wt_i(&flags[kFlagFallback], 1);
             double r = 0.0;
@@ -1487,33 +1536,58 @@ __device__ __forceinline__ int64_t positions_upto(const double v, const int64_t 
 // in the run its carry (carry[fb] = j); positions past the last cumulative
 // weight (the reference's IndexError) are marked with j = n.  The fused block
 // then reads its marks and carry and takes a running max -- no search.
-// wt: the folded data were handed over inside the same launch.
-__device__ void wave_tile_expand(const int64_t b, const int64_t tile, const TileScan& ts,
-                                 const int64_t n,
-                                 const uint64_t* __restrict__ boffk,
-                                 const int32_t* __restrict__ bofff, const uint64_t kofs,
-                                 const int32_t fofs, const SpecialOut* __restrict__ so,
+// bkb, bfb: the block's global offsets (boffk[b], bofff[b]).  SO reads folded
+// special m: SoPlain after a launch boundary, SoTagged inside the merged
+// launch, where a special that never arrives (`lost`) makes the wave skip its
+// tile with status bit 3.
+struct SoPlain {
+    const SpecialOut* __restrict__ so;
+    __device__ __forceinline__ SpecialOut operator()(const int32_t m, bool&) const { return so[m]; }
+};
+struct SoTagged {
+    const uint64_t* __restrict__ tag;
+    uint32_t epoch;
+    int32_t m0;              // the special of the block's record (the one before the block)
+    SpecialOut p0;
+    __device__ __forceinline__ SpecialOut operator()(const int32_t m, bool& lost) const {
+        return m == m0 ? p0 : ld_spec_tagged(tag, m, epoch, lost);
+    }
+};
+template <typename SO>
+__device__ void wave_tile_expand(const int64_t tile, const TileScan& ts, const int64_t n,
+                                 const uint64_t bkb, const int32_t bfb, const uint64_t kofs,
+                                 const int32_t fofs, const SO& ld_so, int32_t* __restrict__ flags,
                                  double* __restrict__ c, int64_t* __restrict__ mark,
                                  int32_t* __restrict__ carry, const double ofs, const int64_t gen,
-                                 const PredictConst& pc, const bool wt, const bool store_c = true) {
+                                 const PredictConst& pc, const bool store_c = true) {
     const int lane = threadIdx.x & 63;
-    auto ld_so = [wt, so](const int32_t m) { return wt ? ld_wt_struct(&so[m]) : so[m]; };
-    const uint64_t bk0 = (wt ? ld_wt(&boffk[b]) : boffk[b]) + kofs;   // the tile's global offsets
-    const int32_t bf0 = (wt ? ld_wt_i(&bofff[b]) : bofff[b]) + fofs;
+    const uint64_t bk0 = bkb + kofs;                // the tile's global offsets
+    const int32_t bf0 = bfb + fofs;
     uint64_t kin = bk0 + ts.kex;
     int32_t m = bf0 + ts.fex;
     double out[kScanPer];
-    SpecialOut p = ld_so(m > 0 ? m - 1 : 0);
+    bool lost = false;
+    SpecialOut p = ld_so(m > 0 ? m - 1 : 0, lost);
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) {
         kin += ts.kk[k];
         if (ts.ff[k]) {
-            p = ld_so(m);
+            p = ld_so(m, lost);
             out[k] = p.cs;
             ++m;
         } else {
             out[k] = p.cs + (double)(kin - p.P) * ldexp(1.0, p.E - 52);
         }
+    }
+    // element j0 - 1 of the tile's first lane, from its run's special
+    double cfirst = -__builtin_inf();
+    if (lane == 0 && tile != 0 && mark) {
+        const SpecialOut q = ld_so(bf0 - 1, lost);
+        cfirst = q.cs + (double)(bk0 - q.P) * ldexp(1.0, q.E - 52);
+    }
+    if (__any(lost)) {                             // (never with SoPlain)
+        if (lane == 0) atomicOr(&flags[kFlagStatus], 8);
+        return;
     }
     const int64_t j0 = tile * kWaveTile + 8 * lane;
     if (store_c) {                                 // (the device-decided step needs only the marks)
@@ -1525,14 +1599,7 @@ __device__ void wave_tile_expand(const int64_t b, const int64_t tile, const Tile
     if (!mark) return;
     // ---- inverse map: runs of this lane's elements
     double cprev = __shfl_up(out[kScanPer - 1], 1, 64);
-    if (lane == 0) {
-        if (tile == 0) {
-            cprev = -__builtin_inf();
-        } else {                             // element j0 - 1 from its run's special
-            const SpecialOut q = ld_so(bf0 - 1);
-            cprev = q.cs + (double)(bk0 - q.P) * ldexp(1.0, q.E - 52);
-        }
-    }
+    if (lane == 0) cprev = cfirst;
     int64_t sj = positions_upto(cprev, n, pc.rstep, ofs);
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) {
@@ -1568,9 +1635,11 @@ __device__ void wave_tile_expand(const int64_t b, const int64_t tile, const Tile
     PROBE_MAX(7);
 }
 
-// the last block of pass A: block-total scans, then place + fold
-template <int kC>
-__device__ __forceinline__ void lean_last_block(uint64_t* __restrict__ bk, int32_t* __restrict__ bf,
+// the last block of pass A: block-total scans, then place + fold; HAND (the
+// merged launch): and the hand-off to the waiting blocks -- false if this
+// block's own record could not be formed
+template <int kC, bool HAND = false>
+__device__ __forceinline__ bool lean_last_block(uint64_t* __restrict__ bk, int32_t* __restrict__ bf,
                                                 uint64_t* __restrict__ boffk,
                                                 int32_t* __restrict__ bofff,
                                                 uint64_t* __restrict__ ktot,
@@ -1580,18 +1649,67 @@ __device__ __forceinline__ void lean_last_block(uint64_t* __restrict__ bk, int32
                                                 int32_t* __restrict__ flags,
                                                 const double* __restrict__ w_un,
                                                 const double* __restrict__ s_in,
-                                                const double np_recip, double* __restrict__ c) {
+                                                const double np_recip, double* __restrict__ c,
+                                                uint64_t* __restrict__ hand = nullptr,
+                                                uint64_t* __restrict__ spec_tag = nullptr,
+                                                const uint32_t epoch = 0,
+                                                uint32_t* __restrict__ s_rec = nullptr) {
     __shared__ uint64_t shk[kScanThreads / 64 + 1];
     __shared__ int32_t shf[kScanThreads / 64 + 1];
-    __shared__ int32_t s_off[kFoldTilesLds];
+    constexpr int kTiles = HAND ? kFoldTilesHand : kFoldTilesLds;
+    __shared__ int32_t s_off[kTiles];
+    bool go = true;
     PROBE_AT(1);
-    block_scan_pair<kScanThreads, kC>(bk, boffk, ktot, bf, bofff, nspec, nblocks, shk, shf,
-                                  nblocks <= kFoldTilesLds ? s_off : nullptr);
-    __syncthreads();
-    PROBE_AT(2);
-    lean_place_fold(stage, boffk, bofff, nblocks, ld_wt_i(nspec), ld_wt(ktot), n, spec_out, flags,
-                    w_un, s_in, np_recip, c, s_off);
-    PROBE_AT(4);
+    if constexpr (!HAND) {
+        block_scan_pair<kScanThreads, kC>(bk, boffk, ktot, bf, bofff, nspec, nblocks, shk, shf,
+                                      nblocks <= kTiles ? s_off : nullptr);
+        __syncthreads();
+        PROBE_AT(2);
+        const bool bad = lean_place_fold(stage, boffk, bofff, nblocks, ld_wt_i(nspec), ld_wt(ktot),
+                                         n, spec_out, flags, s_off, kTiles);
+        PROBE_AT(4);
+        lean_fold_finish(bad, n, flags, w_un, s_in, np_recip, c);
+    } else {
+        // the merged launch: the scan leaves every block's offsets in its
+        // hand-off record (they travel while the fold runs), the fold the
+        // specials as tagged granules, and the verdict goes to the replicas;
+        // this block's own nine words come from LDS (a special beyond the
+        // LDS copies: through its tags)
+        __shared__ uint64_t s_offk[kTiles];
+        __shared__ SpecialOut s_so[kFoldSpecLds];
+        const bool in_lds = nblocks <= kTiles;
+        block_scan_pair<kScanThreads, kC>(bk, boffk, ktot, bf, bofff, nspec, nblocks, shk, shf,
+                                      in_lds ? s_off : nullptr, in_lds ? s_offk : nullptr, true);
+        __syncthreads();
+        PROBE_AT(2);
+        const bool bad = lean_place_fold(stage, boffk, bofff, nblocks, ld_wt_i(nspec), ld_wt(ktot),
+                                         n, spec_out, flags, s_off, kTiles, s_offk, spec_tag, epoch,
+                                         s_so, hand);
+        PROBE_AT(4);
+        if (threadIdx.x < kHandReplicas)
+            st_granule(hand + (int64_t)(nblocks + threadIdx.x) * kHandGranules, bad ? 1u : 0u, epoch);
+        bool lost = false;
+        if (threadIdx.x == 0) {
+            const int b = (int)blockIdx.x;
+            const uint64_t k = in_lds ? s_offk[b] : ld_wt(&boffk[b]);
+            const int32_t f = in_lds ? s_off[b] : ld_wt_i(&bofff[b]);
+            const int32_t m = f > 0 ? f - 1 : 0;
+            const SpecialOut p = m < kFoldSpecLds ? s_so[m] : ld_spec_tagged(spec_tag, m, epoch, lost);
+            const uint64_t cs = (uint64_t)__double_as_longlong(p.cs);
+            s_rec[kHandK0] = (uint32_t)k;
+            s_rec[kHandK1] = (uint32_t)(k >> 32);
+            s_rec[kHandF] = (uint32_t)f;
+            s_rec[kHandCs0] = (uint32_t)cs;
+            s_rec[kHandCs1] = (uint32_t)(cs >> 32);
+            s_rec[kHandP0] = (uint32_t)p.P;
+            s_rec[kHandP1] = (uint32_t)(p.P >> 32);
+            s_rec[kHandE] = (uint32_t)p.E;
+            s_rec[kHandFallback] = bad ? 1u : 0u;
+        }
+        go = !__syncthreads_or(lost);
+        lean_fold_finish(bad, n, flags, w_un, s_in, np_recip, c);
+    }
+    return go;
 }
 
 // A stand-alone exact cumsum's run marks retired (pf_api.hip retire_scan_marks)
@@ -1653,16 +1771,23 @@ __global__ __launch_bounds__(kScanThreads) void scan_lean_expand_kernel(
     block_tile_offsets(ktile, ftile, kofs, fofs, kblk, fblk);
     PROBE_MAX(9);
     if (tile < ntiles)
-        wave_tile_expand(blockIdx.x, tile, ts, n, boffk, bofff, kofs, fofs, so, c, mark, carry,
-                         ofs, gen, pc, false, force != 0 || !mark);   // (device-decided: marks only)
+        wave_tile_expand(tile, ts, n, boffk[blockIdx.x], bofff[blockIdx.x], kofs, fofs, SoPlain{so},
+                         nullptr, c, mark, carry, ofs, gen, pc,
+                         force != 0 || !mark);                        // (device-decided: marks only)
 }
 
 // Passes A and C in ONE launch (NP up to the co-resident grid, checked on the
-// host): classify and stage; the last block scans, places and folds and then
-// releases the others, which waited on a write-through token with their
-// tiles' classification still in registers, and every wave expands its tile.
-// The wait is bounded: a token that never arrives sets status bit 3 and the
-// block skips its expansion instead of hanging the device.
+// host): classify and stage; the last block scans, places and folds, and what
+// the waiting blocks need of that reaches them as tagged granules
+// (pf_kernels.hpp): a block's offsets on its own line, the folded specials, the
+// fold's verdict in replicas -- polled by a few lanes of the block's wave 0,
+// with no fence on either side and no load behind the hand-off that is not
+// itself tagged; the blocks waited with their tiles' classification still in
+// registers, and every wave expands its tile.  The epoch is the token word + 1, read by every block
+// before it arrives and advanced by the last block, so that no record or
+// special of an earlier launch carries it.  The wait is bounded: a record that
+// never arrives sets status bit 3 and the block skips its expansion instead of
+// hanging the device.
 __global__ __launch_bounds__(kScanThreads) void scan_lean_merged_kernel(
     const double* __restrict__ w_un, const double* __restrict__ s_in, const double np_recip,
     const int64_t n, const double* __restrict__ boff, const double delta,
@@ -1671,11 +1796,17 @@ __global__ __launch_bounds__(kScanThreads) void scan_lean_merged_kernel(
     int32_t* __restrict__ nspec, unsigned* __restrict__ counter, int32_t* __restrict__ flags,
     const int32_t force, SpecialOut* __restrict__ spec_out, double* __restrict__ c,
     const StepIO io, const PredictConst pc, const uint64_t seed, int64_t* __restrict__ mark,
-    int32_t* __restrict__ carry, int32_t* __restrict__ token_word, const int ntiles) {
+    int32_t* __restrict__ carry, int32_t* __restrict__ token_word, uint64_t* __restrict__ hand,
+    uint64_t* __restrict__ spec_tag, const int ntiles) {
     if (!force && flags[kFlagResample] != 1) return;
     __shared__ int s_go;
+    __shared__ uint32_t s_rec[kHandUsed];
+    static_assert(kHandK1 == kHandK0 + 1 && kHandF == kHandK0 + 2 && kHandE == kHandCs0 + 4 &&
+                      kHandFallback == kHandCs0 + kSpecGranules,
+                  "the poll's lanes map onto HandWord in order");
     if (blockIdx.x == 0) PROBE_AT(0);
     const int32_t token = ld_wt_i(token_word) + 1;     // read before this block arrives
+    const uint32_t epoch = (uint32_t)token;
     const double ofs = resample_offset(io.ofs[io.ctr[0]], pc.np_recip, seed, (uint32_t)io.ctr[1]);
     const int64_t gen = (int64_t)(uint32_t)flags[kFlagMarkGen] << 32;
     const int64_t tile = (int64_t)blockIdx.x * kTilesPerBlock + (threadIdx.x >> 6);
@@ -1693,36 +1824,68 @@ __global__ __launch_bounds__(kScanThreads) void scan_lean_merged_kernel(
     }
     PROBE_MAX(12);
     if (arrive_last(counter)) {
-        lean_last_block<4>(bk, bf, boffk, bofff, ktot, nspec, (int)gridDim.x, stage, n, spec_out,
-                        flags, w_un, s_in, np_recip, c);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        const bool go = lean_last_block<4, true>(bk, bf, boffk, bofff, ktot, nspec, (int)gridDim.x,
+                                                 stage, n, spec_out, flags, w_un, s_in, np_recip, c,
+                                                 hand, spec_tag, epoch, s_rec);
         if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            st_wt_i(token_word, token);
-            s_go = 1;
+            st_wt_i(token_word, token);               // the next launch's epoch differs
+            if (!go) atomicOr(&flags[kFlagStatus], 8);
+            s_go = go;
         }
-    } else if (threadIdx.x == 0) {
-        int go = 0;
-        for (int it = 0; it < (1 << 22); ++it) {
-            if (ld_wt_i(token_word) == token) {
+    } else if (threadIdx.x < 64) {
+        // wave 0 gathers the block's nine words: lanes 0..2 its own record's
+        // offsets (there long before the fold ends), then lanes 0..4 the
+        // special before the block and lane 5 the verdict (its replica)
+        const uint64_t* rec = hand + (int64_t)blockIdx.x * kHandGranules;
+        const int lane = threadIdx.x;
+        uint64_t g = 0;
+        int go = 0, it = 0;
+        for (; it < kHandSpin; ++it) {
+            if (lane < 3) g = ld_wt(rec + lane);
+            if (__all(lane >= 3 || (uint32_t)(g >> 32) == epoch)) {
                 go = 1;
                 break;
             }
             __builtin_amdgcn_s_sleep(2);
         }
-        if (!go) atomicOr(&flags[kFlagStatus], 8);   // token never came: skip, do not hang
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_go = go;
+        if (lane < 3) s_rec[kHandK0 + lane] = (uint32_t)g;
+        const int32_t bfb = __builtin_amdgcn_readlane((int32_t)(uint32_t)g, kHandF);
+        const int64_t m0 = bfb > 0 ? bfb - 1 : 0;
+        const uint64_t* src = lane < kSpecGranules
+                                  ? spec_tag + m0 * kSpecGranules + lane
+                                  : hand + (int64_t)(gridDim.x + blockIdx.x % kHandReplicas) * kHandGranules;
+        if (go) {
+            go = 0;
+            for (; it < kHandSpin; ++it) {
+                if (lane <= kSpecGranules) g = ld_wt(src);
+                if (__all(lane > kSpecGranules || (uint32_t)(g >> 32) == epoch)) {
+                    go = 1;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(2);
+            }
+        }
+        if (lane <= kSpecGranules) s_rec[kHandCs0 + lane] = (uint32_t)g;
+        if (lane == 0) {
+            if (!go) atomicOr(&flags[kFlagStatus], 8);   // never came: skip, do not hang
+            s_go = go;
+        }
     }
     __syncthreads();
     if (blockIdx.x == 0) PROBE_AT(5);
-    if (!active || !s_go || ld_wt_i(&flags[kFlagFallback])) return;
-    wave_tile_expand(blockIdx.x, tile, ts, n, boffk, bofff, kofs, fofs, spec_out, c, mark, carry,
-                     ofs, gen, pc,
-                     true, force != 0);
+    if (!active || !s_go || s_rec[kHandFallback]) return;
+    const uint64_t bkb = ((uint64_t)s_rec[kHandK1] << 32) | s_rec[kHandK0];
+    const int32_t bfb = (int32_t)s_rec[kHandF];
+    SoTagged so;
+    so.tag = spec_tag;
+    so.epoch = epoch;
+    so.m0 = bfb > 0 ? bfb - 1 : 0;
+    so.p0.cs = __longlong_as_double((long long)(((uint64_t)s_rec[kHandCs1] << 32) | s_rec[kHandCs0]));
+    so.p0.P = ((uint64_t)s_rec[kHandP1] << 32) | s_rec[kHandP0];
+    so.p0.E = (int32_t)s_rec[kHandE];
+    so.p0.pad = 0;
+    wave_tile_expand(tile, ts, n, bkb, bfb, kofs, fofs, so, flags, c, mark, carry, ofs, gen, pc,
+                     force != 0);
 }
 
 // gather for the stand-alone resampling stage (particle_filter.py:216-222)
