@@ -399,6 +399,34 @@ int slam_ekfslam_step(slam_ekfslam* h, const double* control, int32_t k, const i
  * rank-3k covariance update, 0}. */
 int slam_ekfslam_timing(slam_ekfslam* h, double* out);
 
+/* What a handle holds and which kernels its last update launched (recorded
+ * where slam_ekfslam_update takes the branch; all three are 0 before the first
+ * update). */
+enum { SLAM_EKS_RANK_NONE = 0,
+       SLAM_EKS_RANK_FRAG_2X4 = 1,     /* fragment-streaming, 8 waves of 32 x 64 (default, M <= 64) */
+       SLAM_EKS_RANK_FRAG_2X2 = 2,     /* fragment-streaming, 16 waves of 32 x 32 (SLAM_EKS_KERNEL=frag16) */
+       SLAM_EKS_RANK_FRAG_2X4_PF = 3,  /* 2 x 4 with a moved P prefetch (SLAM_EKS_KERNEL=pfmid|pf0, M = 60) */
+       SLAM_EKS_RANK_PIPE = 4,         /* pipelined, LDS operands (SLAM_EKS_KERNEL=pipe, M <= 64) */
+       SLAM_EKS_RANK_LDS = 5 };        /* LDS-staged in k-chunks of 32 (M > 64) */
+enum { SLAM_EKS_APPLY_NONE = 0,
+       SLAM_EKS_APPLY_MFMA = 1,        /* K = PH^T S^-1 by MFMA tiles (M <= 64) */
+       SLAM_EKS_APPLY_LDS = 2 };       /* one wave per row, S^-1 in LDS (M > 64 or SLAM_EKS_APPLY=lds) */
+
+typedef struct {
+    int64_t n;            /* state size 3 + 3 n_landmarks */
+    int64_t ld;           /* row pitch of P in doubles */
+    int64_t n_pad;        /* n rounded up to the 128-row tile */
+    int64_t n_tiles;      /* 128 x 128 tiles of the lower triangle */
+    int64_t frag_grid;    /* resident grid of the fragment-streaming rank update */
+    int64_t pipe_grid;    /* resident grid of the pipelined rank update */
+    int32_t last_m;       /* operand width M = 4 ceil(3k / 4) of the last update */
+    int32_t last_rank;    /* SLAM_EKS_RANK_* of the last update */
+    int32_t last_apply;   /* SLAM_EKS_APPLY_* of the last update */
+    int32_t pad0;
+} slam_ekfslam_info_t;
+
+int slam_ekfslam_info(slam_ekfslam* h, slam_ekfslam_info_t* out);
+
 /* ====================================================================
  * FastSLAM 1.0 with known data association (an extension: the reference's
  * particle filter localises against a known map).  Every particle carries a

@@ -52,6 +52,9 @@ struct slam_ekfslam {
     double* diag = nullptr;        // n (init_diag staging)
     hipEvent_t ev[6] = {};
     double last_ms[5] = {0, 0, 0, 0, 0};
+    int32_t last_m = 0;            // slam_ekfslam_info: the last update's operand width
+    int32_t last_rank = SLAM_EKS_RANK_NONE;     // ... and the kernels it launched
+    int32_t last_apply = SLAM_EKS_APPLY_NONE;
 };
 
 namespace {
@@ -142,6 +145,7 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
         SLAM_ARG_CHECK(ids[t] >= 0 && ids[t] < h->n_lm, "slam_ekfslam_update: landmark id out of range");
     const int32_t m = 3 * k;
     const int32_t M = (m + 3) / 4 * 4;
+    h->last_m = M;
     EksObs ob{};
     for (int32_t t = 0; t < k; ++t) ob.ids[t] = ids[t];
     for (int32_t u = 0; u < 3 * k; ++u) ob.obs[u] = obs[u];
@@ -160,9 +164,11 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
     if (M <= 64 && !h->apply_lds) {
         hipLaunchKernelGGL(eks_apply_mfma_kernel, dim3((unsigned)((h->n_pad / 16 + 3) / 4)), dim3(256),
                            0, h->stream, h->pht, h->sinv, h->e, h->n, h->n_pad, M, h->kg, h->mu);
+        h->last_apply = SLAM_EKS_APPLY_MFMA;
     } else {
         hipLaunchKernelGGL(eks_apply_kernel, dim3((unsigned)apply_grid), dim3(kEksApplyThreads),
                            sbytes, h->stream, h->pht, h->sinv, h->e, h->n, h->n_pad, M, h->kg, h->mu);
+        h->last_apply = SLAM_EKS_APPLY_LDS;
     }
     SLAM_HIP_TRY(hipEventRecord(h->ev[3], h->stream));
     const int64_t nt = h->n_pad / kEksTile;
@@ -180,15 +186,25 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
                        h->kf, h->hf, h->n_pad, tiles)
 #define SLAM_EKS_FRAG(QQ)                                                                         \
     case QQ:                                                                                      \
-        if (h->frag_shape == 1) SLAM_EKS_FRAG_S(QQ, 2, 2); else SLAM_EKS_FRAG_S(QQ, 2, 4);          \
+        if (h->frag_shape == 1) {                                                                 \
+            SLAM_EKS_FRAG_S(QQ, 2, 2);                                                            \
+            h->last_rank = SLAM_EKS_RANK_FRAG_2X2;                                                \
+        } else {                                                                                  \
+            SLAM_EKS_FRAG_S(QQ, 2, 4);                                                            \
+            h->last_rank = SLAM_EKS_RANK_FRAG_2X4;                                                \
+        }                                                                                         \
         break
 #define SLAM_EKS_FRAG_P(QQ, PF)                                                                   \
     hipLaunchKernelGGL((eks_rank_update_frag_kernel<QQ, 2, 4, PF>), dim3((unsigned)h->frag_grid), \
                        dim3(EksFragShape<2, 4>::kThreads), 0, h->stream, h->P, h->n, h->ld,        \
                        h->kf, h->hf, h->n_pad, tiles)
-        if (M / 4 == 15 && h->frag_pf == 1) SLAM_EKS_FRAG_P(15, 7);
-        else if (M / 4 == 15 && h->frag_pf == 2) SLAM_EKS_FRAG_P(15, 0);
-        else switch (M / 4) {
+        if (M / 4 == 15 && h->frag_pf == 1) {
+            SLAM_EKS_FRAG_P(15, 7);
+            h->last_rank = SLAM_EKS_RANK_FRAG_2X4_PF;
+        } else if (M / 4 == 15 && h->frag_pf == 2) {
+            SLAM_EKS_FRAG_P(15, 0);
+            h->last_rank = SLAM_EKS_RANK_FRAG_2X4_PF;
+        } else switch (M / 4) {
             SLAM_EKS_FRAG(1); SLAM_EKS_FRAG(2); SLAM_EKS_FRAG(3); SLAM_EKS_FRAG(4);
             SLAM_EKS_FRAG(5); SLAM_EKS_FRAG(6); SLAM_EKS_FRAG(7); SLAM_EKS_FRAG(8);
             SLAM_EKS_FRAG(9); SLAM_EKS_FRAG(10); SLAM_EKS_FRAG(11); SLAM_EKS_FRAG(12);
@@ -202,10 +218,12 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
         hipLaunchKernelGGL(eks_rank_update_pipelined_kernel, dim3((unsigned)h->pipe_grid),
                            dim3(kEksPipeThreads), 0, h->stream, h->P, h->n, h->ld, h->kg, h->pht, M,
                            tiles);
+        h->last_rank = SLAM_EKS_RANK_PIPE;
     } else {
         const int64_t grid = (tiles + 7) / 8 * 8;
         hipLaunchKernelGGL(eks_rank_update_kernel, dim3((unsigned)grid), dim3(kEksThreads), 0,
                            h->stream, h->P, h->n, h->ld, h->kg, h->pht, M, tiles);
+        h->last_rank = SLAM_EKS_RANK_LDS;
     }
     SLAM_HIP_TRY(hipEventRecord(h->ev[4], h->stream));
     SLAM_HIP_TRY(hipGetLastError());
@@ -586,6 +604,24 @@ int slam_ekfslam_step(slam_ekfslam* h, const double* control, int32_t k, const i
 int slam_ekfslam_timing(slam_ekfslam* h, double* out) {
     SLAM_ARG_CHECK(h && out, "slam_ekfslam_timing: NULL argument");
     for (int q = 0; q < 5; ++q) out[q] = h->last_ms[q];
+    return SLAM_OK;
+}
+
+static_assert(sizeof(slam_ekfslam_info_t) == 64, "slamhip/_lib.py EKFSLAMInfo mirrors this layout");
+
+int slam_ekfslam_info(slam_ekfslam* h, slam_ekfslam_info_t* out) {
+    SLAM_ARG_CHECK(h && out, "slam_ekfslam_info: NULL argument");
+    const int64_t nt = h->n_pad / kEksTile;
+    *out = slam_ekfslam_info_t{};
+    out->n = h->n;
+    out->ld = h->ld;
+    out->n_pad = h->n_pad;
+    out->n_tiles = nt * (nt + 1) / 2;
+    out->frag_grid = h->frag_grid;
+    out->pipe_grid = h->pipe_grid;
+    out->last_m = h->last_m;
+    out->last_rank = h->last_rank;
+    out->last_apply = h->last_apply;
     return SLAM_OK;
 }
 

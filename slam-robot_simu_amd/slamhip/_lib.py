@@ -52,6 +52,17 @@ class EKFSLAMConfig(C.Structure):
                 ("pad0", C.c_int32), ("alphas", C.c_double * 6)]
 
 
+class EKFSLAMInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("ld", C.c_int64), ("n_pad", C.c_int64), ("n_tiles", C.c_int64),
+                ("frag_grid", C.c_int64), ("pipe_grid", C.c_int64), ("last_m", C.c_int32),
+                ("last_rank", C.c_int32), ("last_apply", C.c_int32), ("pad0", C.c_int32)]
+
+
+# slam_ekfslam_info_t.last_rank / last_apply (SLAM_EKS_RANK_*, SLAM_EKS_APPLY_*)
+EKS_RANK = {0: None, 1: "frag2x4", 2: "frag2x2", 3: "frag2x4_pf", 4: "pipe", 5: "lds"}
+EKS_APPLY = {0: None, 1: "mfma", 2: "lds"}
+
+
 class FSConfig(C.Structure):
     _fields_ = [("pf", PFConfig), ("r_dist", C.c_double), ("r_dir", C.c_double),
                 ("r_orient", C.c_double), ("use_orient", C.c_int32), ("pad0", C.c_int32)]
@@ -181,6 +192,7 @@ SIGNATURES = {
     "slam_ekfslam_update": (C.c_int, [_P, C.c_int32, _I64, _D]),
     "slam_ekfslam_step": (C.c_int, [_P, _D, C.c_int32, _I64, _D]),
     "slam_ekfslam_timing": (C.c_int, [_P, _D]),
+    "slam_ekfslam_info": (C.c_int, [_P, C.POINTER(EKFSLAMInfo)]),
     "slam_fs_check_observations": (C.c_int, [C.c_int32, C.c_int32, _I64, _D]),
     "slam_fs_create": (C.c_int, [C.POINTER(FSConfig), C.c_int64, C.c_int32, C.c_int, C.POINTER(_P)]),
     "slam_fs_destroy": (C.c_int, [_P]),

@@ -200,3 +200,14 @@ class DeviceEKFSLAM:
         out = np.zeros(5)
         check(self._lib.slam_ekfslam_timing(self._h, dptr(out)), "slam_ekfslam_timing")
         return dict(gather_ms=out[0], inverse_ms=out[1], gain_ms=out[2], rank_update_ms=out[3])
+
+    def info(self):
+        """Sizes and resident grids of the handle, and of the last update its
+        operand width ``M`` and the kernels it launched: ``rank`` in
+        frag2x4 | frag2x2 | frag2x4_pf | pipe | lds, ``apply`` in mfma | lds
+        (both None before the first update)."""
+        s = _lib.EKFSLAMInfo()
+        check(self._lib.slam_ekfslam_info(self._h, C.byref(s)), "slam_ekfslam_info")
+        return dict(n=s.n, ld=s.ld, n_pad=s.n_pad, n_tiles=s.n_tiles, frag_grid=s.frag_grid,
+                    pipe_grid=s.pipe_grid, M=s.last_m, rank=_lib.EKS_RANK[s.last_rank],
+                    apply=_lib.EKS_APPLY[s.last_apply])

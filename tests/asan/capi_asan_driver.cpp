@@ -137,6 +137,8 @@ int main() {
     EXPECT_ERR(slam_ekfslam_create(nullptr, 10, 0, &eks));
     EXPECT_ERR(slam_ekfslam_predict(nullptr, buf.data()));
     EXPECT_ERR(slam_ekfslam_get_rows(nullptr, 1, &i64, buf.data()));
+    slam_ekfslam_info_t eks_info;
+    EXPECT_ERR(slam_ekfslam_info(nullptr, &eks_info));
     CHECK(slam_ekfslam_destroy(nullptr) == 0, "ekfslam destroy(NULL)");
     slam_graph* gr = nullptr;
     EXPECT_ERR(slam_graph_create(nullptr, 0, &gr));

@@ -45,6 +45,7 @@ def test_struct_layouts():
     from slamhip import _lib
     assert ctypes.sizeof(_lib.PFConfig) == 8 * (1 + 1 + 4 + 9 + 6 + 3 + 1) + 8
     assert ctypes.sizeof(_lib.PFResult) == 8 * (3 + 9 + 3 + 1) + 24
+    assert ctypes.sizeof(_lib.EKFSLAMInfo) == 8 * 6 + 4 * 4
 
 
 def test_create_without_device_fails_loudly():

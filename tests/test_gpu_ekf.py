@@ -16,6 +16,7 @@ import pytest
 
 import ekf_oracle as eo
 from conftest import golden
+from ekfslam_ref import slam_world as _slam_world
 
 pytestmark = pytest.mark.gpu
 
@@ -82,17 +83,6 @@ def test_step_with_control_matches_oracle():
         _, x, P = eo.ekf_update(x, P, z, p, control=ctl)
         np.testing.assert_allclose(xh[:, 0], x, rtol=1e-11, atol=1e-12)
         np.testing.assert_allclose(Pg, P, rtol=1e-10, atol=1e-15)
-
-
-def _slam_world(n_lm, seed):
-    rs = np.random.RandomState(seed)
-    lm = np.column_stack([rs.uniform(-30, 30, (n_lm, 2)), rs.uniform(-np.pi, np.pi, n_lm)])
-    mu = np.concatenate([[0.0, 0.0, 0.3], (lm + rs.normal(0, 0.2, lm.shape)).ravel()])
-    n = mu.size
-    A = rs.normal(0, 0.02, (n, n // 3 + 1))
-    P = A @ A.T + np.diag(np.concatenate([[0.01, 0.01, 0.002], np.full(n - 3, 0.04)]))
-    P = 0.5 * (P + P.T)
-    return rs, lm, mu, P
 
 
 @pytest.mark.parametrize("n_lm,k,steps", [(50, 8, 12), (300, 20, 5), (700, 40, 3)])

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import ekf_oracle as eo
+from ekfslam_ref import slam_world as _slam_world
 
 pytestmark = pytest.mark.gpu
 
@@ -78,17 +79,6 @@ def test_velocity_prediction_is_not_the_linear_one():
         finally:
             dev.close()
     assert not np.allclose(out[0][0], out[1][0])
-
-
-def _slam_world(n_lm, seed):
-    rs = np.random.RandomState(seed)
-    lm = np.column_stack([rs.uniform(-30, 30, (n_lm, 2)), rs.uniform(-np.pi, np.pi, n_lm)])
-    mu = np.concatenate([[0.0, 0.0, 0.3], (lm + rs.normal(0, 0.2, lm.shape)).ravel()])
-    n = mu.size
-    A = rs.normal(0, 0.02, (n, n // 3 + 1))
-    P = A @ A.T + np.diag(np.concatenate([[0.01, 0.01, 0.002], np.full(n - 3, 0.04)]))
-    P = 0.5 * (P + P.T)
-    return rs, lm, mu, P
 
 
 @pytest.mark.parametrize("n_lm,k,steps", [(50, 8, 10), (300, 20, 4)])
