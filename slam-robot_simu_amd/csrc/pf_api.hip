@@ -372,13 +372,21 @@ int launch_fused(slam_pf* h, int motion, bool host_noise) {
     tic(h, 0);
     const double* w_in = h->deferred ? nullptr : h->w;     // deferred: read from w_un
     const double* nsrc = h->noise_src ? h->noise_src : h->noise;
-#define SLAM_FUSED_D(M, L, HN, D)                                                                \
-    pf_fused_kernel<M, L, HN, D><<<g, 256, 0, s>>>(n, h->x[src], h->y[src], h->th[src],         \
-                                                   h->x[dst], h->y[dst], h->th[dst], w_in,      \
-                                                   h->w_un, h->c, h->flags, nsrc, h->lm, io,     \
-                                                   h->pc, h->lc, h->cfg.seed, h->s_cur, h->refp, \
-                                                   h->dp)
-#define SLAM_FUSED(M, L, HN) SLAM_FUSED_D(M, L, HN, true)     /* every handle is deferred */
+#define SLAM_FUSED_D(M, L, HN, D, WT)                                                            \
+    pf_fused_kernel<M, L, HN, D, WT><<<g, 256, 0, s>>>(n, h->x[src], h->y[src], h->th[src],     \
+                                                       h->x[dst], h->y[dst], h->th[dst], w_in,  \
+                                                       h->w_un, h->c, h->flags, nsrc, h->lm, io, \
+                                                       h->pc, h->lc, h->cfg.seed, h->s_cur,      \
+                                                       h->refp, h->dp)
+    // every handle is deferred; write-through pair stores while the launch's
+    // output (32 B per particle) fits the L2s, plain stores above
+#if SLAM_FUSED_WT == 1
+    const bool wt = n <= SLAM_FUSED_WT_MAX;
+#define SLAM_FUSED(M, L, HN)                                                                     \
+    do { if (wt) SLAM_FUSED_D(M, L, HN, true, true); else SLAM_FUSED_D(M, L, HN, true, false); } while (0)
+#else
+#define SLAM_FUSED(M, L, HN) SLAM_FUSED_D(M, L, HN, true, SLAM_FUSED_WT == 2)
+#endif
     if (motion == kMotionNone) {
         if (lik == SLAM_LIK_PRODUCT) SLAM_FUSED(2, 0, false); else SLAM_FUSED(2, 1, false);
     } else if (motion == SLAM_MOTION_LINEAR) {

@@ -196,6 +196,30 @@ __device__ __forceinline__ void st_wt_i(int32_t* p, int32_t v) {
 __device__ __forceinline__ int32_t ld_wt_i(const int32_t* p) {
     return __hip_atomic_load((int32_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// SLAM_FUSED_WT (A/B switch, default 1): the deferred fused kernel's pair
+// stores (x, y, th, w_un) write through on handles of at most
+// SLAM_FUSED_WT_MAX particles -- the launch's output, 32 B per particle, then
+// fits the 32 MiB of L2 -- and are plain stores above (the step
+// is 2.7 % shorter at 2^20, even at 2^21, 1-4 % longer at 2^22 and 2^23);
+// 0 = plain stores always, 2 = write-through always.
+#ifndef SLAM_FUSED_WT
+#define SLAM_FUSED_WT 1
+#endif
+#ifndef SLAM_FUSED_WT_MAX
+#define SLAM_FUSED_WT_MAX (1 << 20)
+#endif
+// A particle pair (16 bytes, 16-byte aligned) as one write-through vector
+// store: the line goes to memory while the kernel runs and is dropped from
+// the XCD's L2, so nothing of it is left dirty for the kernel boundary to
+// write back.  A wave's 64 pairs are eight whole 128-byte lines.
+// The compiler does not pad an asm statement's hazards: the trailing s_nop
+// keeps the next instruction off the data registers until the store has read
+// them.  No wait and no fence: the next reader is the next launch.
+__device__ __forceinline__ void st_wt_pair(double* p, const double a, const double b) {
+    typedef double f64x2_t __attribute__((ext_vector_type(2)));
+    const f64x2_t v = {a, b};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
 template <typename S>
 __device__ __forceinline__ void st_wt_struct(S* dst, const S& v) {
     static_assert(sizeof(S) % 8 == 0, "8-byte granules");

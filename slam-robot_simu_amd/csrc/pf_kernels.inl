@@ -24,7 +24,7 @@ namespace slam {
 #endif
 // One fused block's tile (blk: 256 lanes x P particles): the body of
 // pf_fused_kernel (a persistent grid walking tiles measured slower: DESIGN 4.4).
-template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER>
+template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER, bool WT>
 __device__ __forceinline__ void pf_fused_tile(
     const int64_t blk, const int32_t st, const uint32_t rstep, const int32_t rflag,
     const double* __restrict__ zs, const int wave_s, const RngTabs& rtab,
@@ -36,6 +36,16 @@ __device__ __forceinline__ void pf_fused_tile(
     const uint64_t seed, const double* __restrict__ s_in, const double* __restrict__ refp,
     const DeferParts& dp) {
     constexpr int P = DEFER ? kDeferPPT : 1;
+    // the deferred path's pair stores: write-through (WT: st_wt_pair), so
+    // that the launch leaves none of its 32 B per particle dirty in L2 for the
+    // kernel's end to write back, or plain.  A template flag and not a branch:
+    // the compiler takes the asm store for a write to any address and turns
+    // the wave-uniform loads behind it into per-lane ones, which the large
+    // handles' launches pay for without gaining.
+    auto st_pair = [](double* p, const double a, const double b) {
+        if constexpr (WT) st_wt_pair(p, a, b);
+        else *reinterpret_cast<double2*>(p) = double2{a, b};
+    };
     const int64_t base = blk * (256 * P);
     const int64_t i0 = base + P * (int64_t)threadIdx.x;
     bool valid[P];
@@ -226,12 +236,20 @@ __device__ __forceinline__ void pf_fused_tile(
     for (int k = 0; k < P; ++k)
         predict_particle<MOTION>(x[k], y[k], th[k], v, om, g[k][0], g[k][1], g[k][2], pc, xv[k],
                                  yv[k], tv[k], sp[k], cp[k], rtab);
-    if (DEFER) {                       // padded arrays: the pair is stored whole
+    // padded arrays: the pair is stored whole.  The log-sum kernel's
+    // write-through stores wait for the likelihood (kLate): behind an asm store
+    // the compiler re-reads the closed form's wave-uniform words with vector
+    // loads, and the wait for those is a wait for the stores before them (one
+    // in-order counter) -- the drain this path is meant to avoid
+    constexpr bool kLate = WT && LIK != SLAM_LIK_PRODUCT;
+    if (DEFER) {
+        if constexpr (!kLate) {
 #pragma unroll
-        for (int h = 0; h < P; h += 2) {
-            *reinterpret_cast<double2*>(xo + i0 + h) = double2{xv[h], xv[h + 1]};
-            *reinterpret_cast<double2*>(yo + i0 + h) = double2{yv[h], yv[h + 1]};
-            *reinterpret_cast<double2*>(to + i0 + h) = double2{tv[h], tv[h + 1]};
+            for (int h = 0; h < P; h += 2) {
+                st_pair(xo + i0 + h, xv[h], xv[h + 1]);
+                st_pair(yo + i0 + h, yv[h], yv[h + 1]);
+                st_pair(to + i0 + h, tv[h], tv[h + 1]);
+            }
         }
     } else if (valid[0]) {
         xo[i0] = xv[0];
@@ -263,9 +281,16 @@ __device__ __forceinline__ void pf_fused_tile(
 #pragma unroll
     for (int k = 0; k < P; ++k) wv[k] = valid[k] ? pw[k] * bn[k] : 0.0;   // particle_filter.py:194
     if constexpr (DEFER) {
+        if constexpr (kLate) {
 #pragma unroll
-        for (int h = 0; h < P; h += 2)
-            *reinterpret_cast<double2*>(w_un + i0 + h) = double2{wv[h], wv[h + 1]};
+            for (int h = 0; h < P; h += 2) {
+                st_pair(xo + i0 + h, xv[h], xv[h + 1]);
+                st_pair(yo + i0 + h, yv[h], yv[h + 1]);
+                st_pair(to + i0 + h, tv[h], tv[h + 1]);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < P; h += 2) st_pair(w_un + i0 + h, wv[h], wv[h + 1]);
 #ifndef SLAM_NO_EPILOGUE
         defer_epilogue(base, n, wv, xv, yv, tv, refp, dp, wave_s, (int)blk);
 #endif
@@ -326,11 +351,12 @@ __device__ __forceinline__ void pf_fused_prep_next(const int32_t st, const int w
         __syncthreads();                                                                         \
     }
 
-template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER>
+template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER, bool WT>
 __global__ __launch_bounds__(256) SLAM_FUSED_ATTR void pf_fused_kernel(SLAM_FUSED_PARAMS) {
     static_assert(!DEFER || kDeferPPT % 2 == 0, "the deferred path moves particle pairs");
+    static_assert(DEFER || !WT, "write-through pair stores: the deferred path only");
     SLAM_FUSED_PROLOGUE
-    pf_fused_tile<MOTION, LIK, HOSTNOISE, DEFER>(blockIdx.x, st, rstep, rflag, zs, wave_s, rtab,
+    pf_fused_tile<MOTION, LIK, HOSTNOISE, DEFER, WT>(blockIdx.x, st, rstep, rflag, zs, wave_s, rtab,
                                                  SLAM_FUSED_ARGS);
     if constexpr (DEFER) pf_fused_prep_next<MOTION>(st, wave_s, lm, io, pc, lc, refp);
 }

@@ -83,11 +83,12 @@ def main(src, tag):
             rec["hbm_bytes"] = v["hbm_read_bytes"] + v["hbm_write_bytes"]
         return rec
 
-    key = "pf_fused_kernel<1, 1, false, true>"       # the bench's kernel (velocity, log-sum)
+    # the bench's kernel (velocity, log-sum; the 2^20 handle's write-through instantiation)
+    key = "pf_fused_kernel<1, 1, false, true, true>"
     if key in out and "hbm_read_bytes" in out[key] and "hbm_write_bytes" in out[key]:
         main_rec = summary(key)
         kernels = {}
-        pkey = "pf_fused_kernel<1, 0, false, true>"  # the reference-literal product mode
+        pkey = "pf_fused_kernel<1, 0, false, true, true>"  # the reference-literal product mode
         if pkey in out:
             kernels["product"] = summary(pkey)
         sys.path.insert(0, os.getcwd())

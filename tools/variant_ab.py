@@ -5,7 +5,8 @@ steps, 5 warm-up, 50 timed steps, then an event pass over 49 more.
 
     python tools/variant_ab.py ROUNDS LIB [LIB ...]      (LIB: file name under slamhip/)
     VB_LIK=product for the product likelihood; VB_ESS=<threshold> (0: never resample);
-    VB_NP=<particles> (default the bench's 2^20)
+    VB_NP=<particles> (default the bench's 2^20); VB_SHARDED=1 for the sharded
+    step on one shard (the bench's sharded1 row)
 """
 import os
 import subprocess
@@ -27,6 +28,21 @@ def child():
     ctl = np.tile([vel, omega], (total, 1))
     kw = {"ess_threshold": float(os.environ["VB_ESS"])} if "VB_ESS" in os.environ else {}
     n = int(os.environ.get("VB_NP", bench.NP_PER_GPU))
+    if os.environ.get("VB_SHARDED") == "1":          # the bench's sharded1 row: one shard, in-process
+        from slamhip.dist import DistFilter
+        pf = DistFilter(n, lm, world=1, dt=dt, motion="velocity",
+                        likelihood=os.environ.get("VB_LIK", "logsum"), seed=3)
+        pf.load_observations(zs)
+        pf.prepare_graphs()
+        s0 = bench.settle(pf.run, ctl, settle)
+        pf.run(s0, ctl[s0:s0 + warm], want_results=False)
+        t0 = time.perf_counter()
+        pf.run(s0 + warm, ctl[s0 + warm:s0 + warm + steps])
+        el = time.perf_counter() - t0
+        pf.close()
+        print(f"{os.path.basename(os.environ.get('SLAM_HIP_LIB', 'default'))}: sharded1 step "
+              f"{el / steps * 1e3:.4f} ms", flush=True)
+        return
     pf = DeviceParticleFilter(n, lm, dt=dt, motion="velocity",
                               likelihood=os.environ.get("VB_LIK", "logsum"), seed=3, **kw)
     pf.load_observations(zs)
