@@ -429,7 +429,8 @@ int slam_ekfslam_info(slam_ekfslam* h, slam_ekfslam_info_t* out);
 
 /* ====================================================================
  * FastSLAM 1.0 with known data association (an extension: the reference's
- * particle filter localises against a known map).  Every particle carries a
+ * particle filter localises against a known map); per-particle
+ * maximum-likelihood association follows below.  Every particle carries a
  * pose, a weight and, per landmark, a mean (mx, my) and a symmetric 2 x 2
  * covariance (pxx, pxy, pyy) -- one small EKF per particle and landmark.  A
  * step observes any k <= NL landmarks (ScanSensor's range, bearing,
@@ -519,6 +520,63 @@ int slam_fs_run(slam_fs* h, int32_t first_step, int32_t n_steps, const double* c
 /* HIP-event time (ms) of the last step's phases: out[4] = {map gather, predict,
  * map update + weights, step end}; 0 for a phase that did not run. */
 int slam_fs_timing(slam_fs* h, double* out);
+
+/* --------------------------------------------------------------------
+ * Per-particle maximum-likelihood data association.  A range / bearing
+ * sensor returns (d, phi, psi) triples with no identity; an associating
+ * handle lets every particle decide for itself which of its own landmarks an
+ * observation belongs to.  Particle p holds cnt_p <= cap landmarks in slots
+ * 0..cnt_p-1 of its map, in the order it created them; landmarks are never
+ * removed.
+ *
+ * A step keeps the order above; resample, predict and the step end are
+ * unchanged (the gather moves the counts with the poses, and the map rows
+ * below a particle's own count).  The update, for every particle, with cnt0_p
+ * the count when the update starts, and for each observation z = (d, phi, psi)
+ * in the order given:
+ *   1. the orientation term as in step 3 above (use_orient);
+ *   2. the candidates are the slots j < cnt0_p that no earlier observation of
+ *      this update has matched in this particle (a scan sees each landmark
+ *      once; a slot created during this update is never a candidate);
+ *   3. l_j = -(e^T S^-1 e + ln det S) / 2 - ln(2 pi), with e, S, H and R of the
+ *      known-association update;
+ *   4. best = the largest l_j, the lowest slot on a tie;
+ *   5. no candidate, or l_best < log_p_new: a new landmark -- slot cnt_p takes
+ *      the first-sighting mean and covariance and cnt_p grows by one, or, when
+ *      cnt_p == cap, the observation is dropped and the map does not change;
+ *      either way L_p += log_p_new;
+ *   6. otherwise slot best takes the EKF update and L_p += l_best.
+ * Then w_un = w exp(L_p - max_p L_p) and the step end as above.
+ *
+ * On an associating handle ids must be NULL in slam_fs_step, slam_fs_update
+ * and slam_fs_load_observations, and 0 <= k <= SLAM_FS_ASSOC_MAX_OBS (not
+ * bounded by cap); d > 0 and finiteness as slam_fs_check_observations; all
+ * checked before any HIP call.  slam_fs_set_maps ignores seen (it may be
+ * NULL); slam_fs_get_maps and slam_fs_get_map return NaN for slots j >= cnt_p,
+ * slam_fs_get_maps reports seen[j] = (j < max_p cnt_p), slam_fs_get_map
+ * seen[j] = (j < cnt_p); slam_fs_info reports n_landmarks = cap and n_seen =
+ * max_p cnt_p.  Every other entry point works as on any handle.
+ * -------------------------------------------------------------------- */
+#define SLAM_FS_ASSOC_MAX_OBS 4096
+
+typedef struct {
+    double log_p_new;     /* log likelihood of "a landmark not in the map yet" (finite) */
+    int32_t record;       /* keep the last update's choices for slam_fs_get_assoc
+                             (4 B x k x n_particles written per update) */
+    int32_t pad0;
+} slam_fs_assoc_config;
+
+/* max_landmarks >= 1 is the capacity cap of every particle's map; beside the
+ * two map halves the handle holds 4 B x cap x n_particles of match stamps. */
+int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                         int64_t n_particles, int32_t max_landmarks, int device, slam_fs** out);
+/* counts[NP], each in [0, cap].  SLAM_ERR_ARG on a known-association handle. */
+int slam_fs_set_counts(slam_fs* h, const int32_t* counts);
+int slam_fs_get_counts(slam_fs* h, int32_t* counts);
+/* out[k][NP], k of the last update (of slam_fs_run: its last step): the slot
+ * matched, -1 for a new landmark, -2 for a dropped observation.  SLAM_ERR_ARG
+ * unless the handle was created with record != 0. */
+int slam_fs_get_assoc(slam_fs* h, int32_t* out);
 
 /* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve

@@ -1,6 +1,7 @@
 // fastslam.inl -- gfx950 kernels of FastSLAM 1.0 with known data association
 // (included by fs_api.inl): the per-particle landmark EKFs with their log
-// weights, the weight pass, and the resampling gather of whole maps.
+// weights, the weight pass, and the resampling gather of whole maps; below
+// them the kernels of per-particle maximum-likelihood association.
 //
 // Map layout: component-major per landmark,
 //     map[(5 j + c) * npad + p],   c = mx, my, pxx, pxy, pyy
@@ -220,6 +221,252 @@ __global__ __launch_bounds__(kFsThreads) void fs_map_unpack_kernel(
         for (int32_t c = 0; c < ncomp; ++c)
             map[((size_t)kFsComp * j + comp0 + c) * (size_t)npad + (size_t)p] =
                 in[((size_t)p * nl + j) * ncomp + c];
+}
+
+// ------------------------------------------------------------------------
+// Per-particle maximum-likelihood data association.  Particle p
+// holds cnt[p] landmarks in slots 0..cnt[p]-1 of the same component-major map;
+// stamp[j * npad + p] is the number of the update call that last matched slot
+// j of particle p (a scan sees each landmark once).
+// ------------------------------------------------------------------------
+constexpr double kFsLn2Pi = 1.8378770664093453;     // np.log(2 * np.pi)
+
+__device__ __forceinline__ int32_t fs_wave_max_i32(int32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int32_t u = __shfl_xor(v, o, 64);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+
+// One lane per particle.  Per observation the wave walks the slots below its
+// largest count: every lane reads the same row (512 contiguous bytes per
+// component, 256 of stamps), lanes past their own count or on a slot already
+// matched in this call are masked.  The best slot is then updated from a
+// re-read of its row by fs_update_kernel's expressions; without a candidate,
+// or below log_p_new, the observation starts slot cnt (dropped at cap).
+// assoc (NULL unless recorded) takes the choice: slot, -1 new, -2 dropped.
+__global__ __launch_bounds__(kFsThreads) void fs_assoc_update_kernel(
+    const int64_t n, const int64_t npad, const double* __restrict__ xs,
+    const double* __restrict__ ys, const double* __restrict__ ts, double* __restrict__ map,
+    int32_t* __restrict__ cnt_io, int32_t* __restrict__ stamp, const int32_t call,
+    const int32_t cap, const int32_t nobs, const FsObs* __restrict__ obs, const int32_t use_orient,
+    const double log_p_new, int32_t* __restrict__ assoc, double* __restrict__ L_out,
+    double* __restrict__ bmax, int32_t* __restrict__ bcnt) {
+    __shared__ double s_d[kFsObsLds], s_phi[kFsObsLds], s_psi[kFsObsLds], s_r0[kFsObsLds],
+        s_r1[kFsObsLds], s_rx[kFsObsLds], s_ry[kFsObsLds], s_vo[kFsObsLds];
+    __shared__ double s_wmax[kFsThreads / 64];
+    __shared__ int32_t s_cmax[kFsThreads / 64];
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    const bool valid = p < n;
+    const int64_t pc = valid ? p : n - 1;
+    const double x = xs[pc], y = ys[pc], th = ts[pc];
+    const double psi_p = kHalfPi - th;
+    double s, c;
+    sincos(psi_p, &s, &c);
+    const double psi_w = wrap_angle(psi_p);
+    const int32_t cnt0 = valid ? cnt_io[p] : 0;     // padding lanes: no candidates, no stores
+    const int32_t jmax = __builtin_amdgcn_readfirstlane(fs_wave_max_i32(cnt0));
+    int32_t cnt = cnt0;
+    double L = 0.0;
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t m_obs = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        __syncthreads();
+        if ((int32_t)threadIdx.x < m_obs) {
+            const FsObs o = obs[base + threadIdx.x];
+            s_d[threadIdx.x] = o.d;
+            s_phi[threadIdx.x] = o.phi;
+            s_psi[threadIdx.x] = o.psi;
+            s_r0[threadIdx.x] = o.r0;
+            s_r1[threadIdx.x] = o.r1;
+            s_rx[threadIdx.x] = o.rx;
+            s_ry[threadIdx.x] = o.ry;
+            s_vo[threadIdx.x] = o.vo;
+        }
+        __syncthreads();
+        for (int32_t t = 0; t < m_obs; ++t) {
+            const double R0 = s_r0[t], R1 = s_r1[t], zd = s_d[t], zphi = s_phi[t];
+            if (use_orient) {
+                const double e = wrap_angle(s_psi[t] - psi_w);
+                L -= e * e / (2.0 * s_vo[t]);
+            }
+            double best = -INFINITY;
+            int32_t bj = -1;
+            for (int32_t j = 0; j < jmax; ++j) {
+                const size_t row = (size_t)kFsComp * (size_t)j * (size_t)npad + (size_t)pc;
+                const int32_t st = stamp[(size_t)j * (size_t)npad + (size_t)pc];
+                const double mx = map[row], my = map[row + (size_t)npad];
+                const double pxx = map[row + 2 * (size_t)npad], pxy = map[row + 3 * (size_t)npad],
+                             pyy = map[row + 4 * (size_t)npad];
+                const double dx = mx - x, dy = my - y;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+                const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+                const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+                const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+                const double s00 = h00 * t00 + h01 * t10 + R0;
+                const double s01 = h00 * t01 + h01 * t11;
+                const double s11 = h10 * t01 + h11 * t11 + R1;
+                const double det = s00 * s11 - s01 * s01;
+                const double e0 = zd - r, e1 = wrap_angle(zphi - bearing);
+                const double maha = (e0 * e0 * s11 - 2.0 * (e0 * e1) * s01 + e1 * e1 * s00) / det;
+                const double l = -(maha + log(det)) / 2.0 - kFsLn2Pi;
+                // strictly greater: a tie keeps the lowest slot; NaN never wins
+                if (j < cnt0 && st != call && l > best) {
+                    best = l;
+                    bj = j;
+                }
+            }
+            int32_t a;
+            if (bj < 0 || best < log_p_new) {
+                L += log_p_new;
+                a = -2;
+                if (cnt < cap) {
+                    double* m = map + (size_t)kFsComp * (size_t)cnt * (size_t)npad + (size_t)pc;
+                    const double rx = s_rx[t], ry = s_ry[t];
+                    const double dx = c * rx + s * ry, dy = -s * rx + c * ry;
+                    const double q = dx * dx + dy * dy, r = sqrt(q);
+                    const double a00 = dx / r, a01 = -dy, a10 = dy / r, a11 = dx;
+                    if (valid) {
+                        m[0] = x + dx;
+                        m[(size_t)npad] = y + dy;
+                        m[2 * (size_t)npad] = a00 * a00 * R0 + a01 * a01 * R1;
+                        m[3 * (size_t)npad] = a00 * a10 * R0 + a01 * a11 * R1;
+                        m[4 * (size_t)npad] = a10 * a10 * R0 + a11 * a11 * R1;
+                    }
+                    a = -1;
+                    ++cnt;
+                }
+            } else {
+                double* m = map + (size_t)kFsComp * (size_t)bj * (size_t)npad + (size_t)pc;
+                const double mx = m[0], my = m[(size_t)npad];
+                const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                             pyy = m[4 * (size_t)npad];
+                const double dx = mx - x, dy = my - y;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+                const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+                const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+                const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+                const double s00 = h00 * t00 + h01 * t10 + R0;
+                const double s01 = h00 * t01 + h01 * t11;
+                const double s11 = h10 * t01 + h11 * t11 + R1;
+                const double det = s00 * s11 - s01 * s01;
+                const double e0 = zd - r, e1 = wrap_angle(zphi - bearing);
+                L += best;
+                const double k00 = (t00 * s11 - t01 * s01) / det, k01 = (t01 * s00 - t00 * s01) / det;
+                const double k10 = (t10 * s11 - t11 * s01) / det, k11 = (t11 * s00 - t10 * s01) / det;
+                const double m00 = k00 * s00 + k01 * s01, m01 = k00 * s01 + k01 * s11;
+                const double m10 = k10 * s00 + k11 * s01, m11 = k10 * s01 + k11 * s11;
+                // bj >= 0 implies a valid lane (padding lanes have no candidates)
+                m[0] = mx + (k00 * e0 + k01 * e1);
+                m[(size_t)npad] = my + (k10 * e0 + k11 * e1);
+                m[2 * (size_t)npad] = pxx - (m00 * k00 + m01 * k01);
+                m[3 * (size_t)npad] = pxy - (m00 * k10 + m01 * k11);
+                m[4 * (size_t)npad] = pyy - (m10 * k10 + m11 * k11);
+                stamp[(size_t)bj * (size_t)npad + (size_t)pc] = call;
+                a = bj;
+            }
+            if (assoc && valid) assoc[(size_t)(base + t) * (size_t)npad + (size_t)p] = a;
+        }
+    }
+    if (valid) {
+        L_out[p] = L;
+        cnt_io[p] = cnt;
+    }
+    const double wm = fs_wave_max(valid ? L : -INFINITY);
+    const int32_t cm = fs_wave_max_i32(valid ? cnt : 0);
+    if ((threadIdx.x & 63) == 0) {
+        s_wmax[threadIdx.x >> 6] = wm;
+        s_cmax[threadIdx.x >> 6] = cm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = s_wmax[0];
+        int32_t u = s_cmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) {
+            v = fmax(v, s_wmax[w]);
+            u = s_cmax[w] > u ? s_cmax[w] : u;
+        }
+        bmax[blockIdx.x] = v;
+        bcnt[blockIdx.x] = u;
+    }
+}
+
+// fs_max_fold_kernel with the block maxima of the counts beside it; the
+// largest count goes to the host's coherent word (read with the step's record)
+__global__ __launch_bounds__(kFsThreads) void fs_assoc_fold_kernel(
+    const double* __restrict__ bmax, const int32_t* __restrict__ bcnt, const int32_t nb,
+    double* __restrict__ gmax, int32_t* __restrict__ cmax_host) {
+    __shared__ double s_wmax[kFsThreads / 64];
+    __shared__ int32_t s_cmax[kFsThreads / 64];
+    double v = -INFINITY;
+    int32_t u = 0;
+    for (int32_t b = threadIdx.x; b < nb; b += kFsThreads) {
+        v = fmax(v, bmax[b]);
+        u = bcnt[b] > u ? bcnt[b] : u;
+    }
+    v = fs_wave_max(v);
+    u = fs_wave_max_i32(u);
+    if ((threadIdx.x & 63) == 0) {
+        s_wmax[threadIdx.x >> 6] = v;
+        s_cmax[threadIdx.x >> 6] = u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        v = s_wmax[0];
+        u = s_cmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) {
+            v = fmax(v, s_wmax[w]);
+            u = s_cmax[w] > u ? s_cmax[w] : u;
+        }
+        *gmax = v;
+        *cmax_host = u;
+    }
+}
+
+// Resampling gather of an associating handle: the counts move with the poses
+// (blockIdx.y == 0), and particle p takes the rows of its source below the
+// source's own count, of the rows below nrows >= max cnt that the grid walks.
+__global__ __launch_bounds__(kFsThreads) void fs_assoc_gather_kernel(
+    const int64_t n, const int64_t npad, const int32_t* __restrict__ idx, const int32_t nrows,
+    const double* __restrict__ src, double* __restrict__ dst, const int32_t* __restrict__ cnt_src,
+    int32_t* __restrict__ cnt_dst) {
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= n) return;
+    const int64_t q = idx[p];
+    const int32_t cq = cnt_src[q];
+    if (blockIdx.y == 0) cnt_dst[p] = cq;
+    const int32_t lim = cq < nrows ? cq : nrows;
+    for (int32_t j = blockIdx.y; j < lim; j += gridDim.y) {
+        const size_t row = (size_t)kFsComp * (size_t)j * (size_t)npad;
+        const double* a = src + row + (size_t)q;
+        double* b = dst + row + (size_t)p;
+        const double v0 = a[0], v1 = a[(size_t)npad], v2 = a[2 * (size_t)npad],
+                     v3 = a[3 * (size_t)npad], v4 = a[4 * (size_t)npad];
+        b[0] = v0;
+        b[(size_t)npad] = v1;
+        b[2 * (size_t)npad] = v2;
+        b[3 * (size_t)npad] = v3;
+        b[4 * (size_t)npad] = v4;
+    }
+}
+
+// fs_map_pack_kernel masked by the particle's own count instead of seen[j]
+__global__ __launch_bounds__(kFsThreads) void fs_assoc_pack_kernel(
+    const int64_t n, const int64_t npad, const int32_t nl, const int64_t p0, const int64_t count,
+    const int32_t comp0, const int32_t ncomp, const int32_t* __restrict__ cnt,
+    const double* __restrict__ map, double* __restrict__ out) {
+    const int64_t p = p0 + (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    if (p >= p0 + count || p >= n) return;
+    const int32_t cp = cnt[p];
+    for (int32_t j = blockIdx.y; j < nl; j += gridDim.y)
+        for (int32_t c = 0; c < ncomp; ++c)
+            out[((size_t)(p - p0) * nl + j) * ncomp + c] =
+                j < cp ? map[((size_t)kFsComp * j + comp0 + c) * (size_t)npad + (size_t)p] : NAN;
 }
 
 }  // namespace slam

@@ -1,5 +1,5 @@
-// fs_api.inl -- C-ABI of FastSLAM 1.0 with known data association
-// (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
+// fs_api.inl -- C-ABI of FastSLAM 1.0, with known data association or with
+// per-particle maximum-likelihood association (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
 // pf_dist_api.inl is: the poses, weights, exact cumsum, systematic resampling,
 // predict and step end are the single handle's own (a slam_pf with zero
 // landmarks); this file adds the per-particle maps, their update with its log
@@ -28,6 +28,20 @@ struct slam_fs {
     std::vector<int64_t> run_off;          // loaded run: record offsets per step, [steps + 1]
     hipEvent_t ev[4][2] = {};
     bool ran[4] = {false, false, false, false};
+    // per-particle association (slam_fs_create_assoc); nl is then the capacity
+    bool assoc = false;
+    slam_fs_assoc_config acfg = {};
+    int32_t* cnt[2] = {nullptr, nullptr};  // ping-pong halves of the counts, [npad]
+    int ccur = 0;
+    int32_t* stamp = nullptr;              // [cap][npad] update call that last matched the slot
+    int32_t call = 0;                      // number of the last update call
+    int32_t* bcnt = nullptr;               // [nb] block maxima of the counts
+    int32_t* cmax_pin = nullptr;           // pinned, coherent: max cnt after the last update
+    int32_t* cmax_pin_dev = nullptr;
+    int32_t cmax = 0;                      // host bound on max cnt (exact after an update)
+    int32_t* assoc_dev = nullptr;          // [assoc_cap][npad] the last update's choices
+    int64_t assoc_cap = 0;
+    int32_t assoc_k = 0;
 };
 
 namespace {
@@ -51,7 +65,23 @@ int fs_check_list(int32_t nl, const char* who, int32_t k, const int64_t* ids, co
     return SLAM_OK;
 }
 
+// An associating handle's list: no ids, k bounded by SLAM_FS_ASSOC_MAX_OBS
+int fs_check_list_assoc(const char* who, int32_t k, const int64_t* ids, const double* obs) {
+    if (ids) return fail(SLAM_ERR_ARG, std::string(who) + ": ids must be NULL on an associating handle");
+    if (k < 0 || k > SLAM_FS_ASSOC_MAX_OBS)
+        return fail(SLAM_ERR_ARG, std::string(who) + ": need 0 <= k <= SLAM_FS_ASSOC_MAX_OBS");
+    if (k > 0 && !obs) return fail(SLAM_ERR_ARG, std::string(who) + ": NULL obs");
+    for (int32_t t = 0; t < k; ++t) {
+        const double d = obs[3 * t], phi = obs[3 * t + 1], psi = obs[3 * t + 2];
+        if (!(std::isfinite(d) && std::isfinite(phi) && std::isfinite(psi)))
+            return fail(SLAM_ERR_ARG, std::string(who) + ": non-finite observation");
+        if (!(d > 0.0)) return fail(SLAM_ERR_ARG, std::string(who) + ": observed range d <= 0");
+    }
+    return SLAM_OK;
+}
+
 int fs_check_obs(slam_fs* f, const char* who, int32_t k, const int64_t* ids, const double* obs) {
+    if (f->assoc) return fs_check_list_assoc(who, k, ids, obs);
     return fs_check_list(f->nl, who, k, ids, obs);
 }
 
@@ -79,6 +109,17 @@ int fs_reserve_obs(slam_fs* f, int64_t count) {
     f->obs_cap = 0;
     SLAM_HIP_TRY(hipMalloc((void**)&f->obs_dev, sizeof(FsObs) * (size_t)count));
     f->obs_cap = count;
+    return SLAM_OK;
+}
+
+int fs_reserve_assoc(slam_fs* f, int64_t k) {
+    if (k <= f->assoc_cap) return SLAM_OK;
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    if (f->assoc_dev) (void)hipFree(f->assoc_dev);
+    f->assoc_dev = nullptr;
+    f->assoc_cap = 0;
+    SLAM_HIP_TRY(hipMalloc((void**)&f->assoc_dev, sizeof(int32_t) * (size_t)k * (size_t)f->npad));
+    f->assoc_cap = k;
     return SLAM_OK;
 }
 
@@ -121,6 +162,19 @@ int fs_enqueue_resample(slam_fs* f, double u) {
     SLAM_HIP_TRY(hipGetLastError());
     if ((rc = set_s_one(h))) return rc;
     h->cur = dst;
+    if (f->assoc) {
+        // the counts with the poses, and every row below a particle's own count
+        fs_tic(f, 0);
+        fs_assoc_gather_kernel<<<fs_grid(f->n, f->cmax), kFsThreads, 0, h->stream>>>(
+            f->n, f->npad, h->idx, f->cmax, f->map[f->mcur], f->map[1 - f->mcur], f->cnt[f->ccur],
+            f->cnt[1 - f->ccur]);
+        SLAM_HIP_TRY(hipGetLastError());
+        f->mcur = 1 - f->mcur;
+        f->ccur = 1 - f->ccur;
+        fs_toc(f, 0);
+        h->resample_next = 0;
+        return set_flag(h, kFlagResample, 0);
+    }
     f->list.clear();
     for (int32_t j = 0; j < f->nl; ++j)
         if (f->seen[(size_t)j]) f->list.push_back(j);
@@ -161,7 +215,22 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
     slam_pf* h = f->pf;
     int rc;
     fs_tic(f, 2);
-    if (k > 0) {
+    if (k > 0 && f->assoc) {
+        const int c = h->cur;
+        int32_t* rec = nullptr;
+        if (f->acfg.record) {
+            if ((rc = fs_reserve_assoc(f, k))) return rc;
+            rec = f->assoc_dev;
+        }
+        ++f->call;
+        fs_assoc_update_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(
+            f->n, f->npad, h->x[c], h->y[c], h->th[c], f->map[f->mcur], f->cnt[f->ccur], f->stamp,
+            f->call, f->nl, k, obs, f->cfg.use_orient, f->acfg.log_p_new, rec, f->L, f->bmax, f->bcnt);
+        fs_assoc_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->bcnt, f->nb, f->bmax + f->nb,
+                                                             f->cmax_pin_dev);
+        fs_weight_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(f->n, f->L, f->bmax + f->nb, h->w_un);
+        SLAM_HIP_TRY(hipGetLastError());
+    } else if (k > 0) {
         const int c = h->cur;
         fs_update_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(
             f->n, f->npad, h->x[c], h->y[c], h->th[c], f->map[f->mcur], k, obs, f->seen_dev,
@@ -171,6 +240,7 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
         fs_mark_seen_kernel<<<grid_for(k, kFsThreads), kFsThreads, 0, h->stream>>>(k, obs, f->seen_dev);
         SLAM_HIP_TRY(hipGetLastError());
     }
+    if (f->assoc) f->assoc_k = k;
     fs_toc(f, 2);
     static const double ctl0[2] = {0.0, 0.0};
     SLAM_HIP_TRY(hipMemcpyAsync(h->ctl, ctl0, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -181,7 +251,13 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
     return SLAM_OK;
 }
 
+// after the step's host read.  An associating handle has no filter-wide
+// "seen": it takes the largest count, which the fold stored beside the record.
 void fs_note_seen(slam_fs* f, int32_t k, const FsObs* obs) {
+    if (f->assoc) {
+        if (k > 0) f->cmax = *f->cmax_pin;
+        return;
+    }
     for (int32_t t = 0; t < k; ++t) f->seen[(size_t)obs[t].id] = 1;
 }
 
@@ -196,13 +272,19 @@ int fs_step_records(slam_fs* f, const double* control, int32_t k, const FsObs* d
     if (resampling && (rc = fs_enqueue_resample(f, u))) return rc;
     if ((rc = fs_enqueue_predict(f, control, noise))) return rc;
     if ((rc = fs_enqueue_update(f, k, dev_obs, resampling))) return rc;
+    if (f->assoc) {
+        rc = sync_results(h, 0, 1, res);    // the step's one host read, the largest count with it
+        fs_note_seen(f, k, host_obs);
+        return rc;
+    }
     fs_note_seen(f, k, host_obs);
     return sync_results(h, 0, 1, res);      // the step's one host read
 }
 
 int fs_stage_step_obs(slam_fs* f, int32_t k, const int64_t* ids, const double* obs) {
     f->obs_host.resize((size_t)k);
-    for (int32_t t = 0; t < k; ++t) f->obs_host[(size_t)t] = fs_make_obs(f, ids[t], obs + 3 * t);
+    for (int32_t t = 0; t < k; ++t)
+        f->obs_host[(size_t)t] = fs_make_obs(f, ids ? ids[t] : -1, obs + 3 * t);
     f->run_off.clear();                     // the device records no longer hold a loaded run
     if (k == 0) return SLAM_OK;
     int rc = fs_reserve_obs(f, k);
@@ -235,9 +317,14 @@ int fs_maps_io(slam_fs* f, bool to_device, double* mean, double* cov) {
                 fs_map_unpack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
                     cnt, f->npad, f->nl, comp0, ncomp, f->stage, f->map[f->mcur] + p0);
             } else {
-                fs_map_pack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
-                    f->n, f->npad, f->nl, p0, cnt, comp0, ncomp, f->seen_dev, f->map[f->mcur],
-                    f->stage);
+                if (f->assoc)
+                    fs_assoc_pack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
+                        f->n, f->npad, f->nl, p0, cnt, comp0, ncomp, f->cnt[f->ccur],
+                        f->map[f->mcur], f->stage);
+                else
+                    fs_map_pack_kernel<<<fs_grid(cnt, f->nl), kFsThreads, 0, h->stream>>>(
+                        f->n, f->npad, f->nl, p0, cnt, comp0, ncomp, f->seen_dev, f->map[f->mcur],
+                        f->stage);
                 SLAM_HIP_TRY(hipMemcpyAsync(hp, f->stage, bytes, hipMemcpyDeviceToHost, h->stream));
             }
             SLAM_HIP_TRY(hipGetLastError());
@@ -246,6 +333,9 @@ int fs_maps_io(slam_fs* f, bool to_device, double* mean, double* cov) {
     }
     return SLAM_OK;
 }
+
+int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, int64_t n_particles,
+                   int32_t n_landmarks, int device, slam_fs** out);
 
 }  // namespace
 
@@ -258,6 +348,27 @@ int slam_fs_check_observations(int32_t n_landmarks, int32_t k, const int64_t* id
 
 int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_landmarks, int device,
                    slam_fs** out) {
+    return fs_create_impl(cfg, nullptr, n_particles, n_landmarks, device, out);
+}
+
+int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                         int64_t n_particles, int32_t max_landmarks, int device, slam_fs** out) {
+    SLAM_ARG_CHECK(cfg && acfg && out, "slam_fs_create_assoc: NULL argument");
+    *out = nullptr;
+    SLAM_ARG_CHECK(n_particles >= 1 && n_particles <= (int64_t(1) << 24),
+                   "slam_fs_create_assoc: need 1 <= n_particles <= 2^24");
+    SLAM_ARG_CHECK(max_landmarks >= 1, "slam_fs_create_assoc: need max_landmarks >= 1");
+    SLAM_ARG_CHECK(std::isfinite(acfg->log_p_new), "slam_fs_create_assoc: non-finite log_p_new");
+    return fs_create_impl(cfg, acfg, n_particles, max_landmarks, device, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// slam_fs_create, and slam_fs_create_assoc's second half (acfg != NULL)
+int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, int64_t n_particles,
+                   int32_t n_landmarks, int device, slam_fs** out) {
     SLAM_ARG_CHECK(cfg && out, "slam_fs_create: NULL argument");
     *out = nullptr;
     SLAM_ARG_CHECK(n_particles >= 1 && n_particles <= (int64_t(1) << 24),
@@ -295,6 +406,26 @@ int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_lan
     if (e == hipSuccess) e = hipMalloc((void**)&f->list_dev, sizeof(int32_t) * (size_t)n_landmarks);
     if (e == hipSuccess)
         e = hipMemsetAsync(f->seen_dev, 0, sizeof(int32_t) * (size_t)n_landmarks, pf->stream);
+    if (acfg) {
+        f->assoc = true;
+        f->acfg = *acfg;
+        f->acfg.record = acfg->record ? 1 : 0;
+        const size_t cb = sizeof(int32_t) * (size_t)f->npad;
+        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+            e = hipMalloc((void**)&f->cnt[k], cb);
+            if (e == hipSuccess) e = hipMemsetAsync(f->cnt[k], 0, cb, pf->stream);
+        }
+        if (e == hipSuccess) e = hipMalloc((void**)&f->stamp, cb * (size_t)n_landmarks);
+        if (e == hipSuccess) e = hipMemsetAsync(f->stamp, 0, cb * (size_t)n_landmarks, pf->stream);
+        if (e == hipSuccess) e = hipMalloc((void**)&f->bcnt, sizeof(int32_t) * (size_t)f->nb);
+        if (e == hipSuccess)
+            e = hipHostMalloc((void**)&f->cmax_pin, sizeof(int32_t),
+                              hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) {
+            *f->cmax_pin = 0;
+            e = hipHostGetDevicePointer((void**)&f->cmax_pin_dev, f->cmax_pin, 0);
+        }
+    }
     for (int k = 0; k < 4 && e == hipSuccess; ++k)
         for (int q = 0; q < 2 && e == hipSuccess; ++q) e = hipEventCreate(&f->ev[k][q]);
     if (e == hipSuccess) e = hipStreamSynchronize(pf->stream);
@@ -306,6 +437,19 @@ int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_lan
     *out = f;
     return SLAM_OK;
 }
+
+// the counts of the current half on the host (synchronises)
+int fs_counts_host(slam_fs* f, std::vector<int32_t>& c) {
+    c.resize((size_t)f->n);
+    SLAM_HIP_TRY(hipMemcpyAsync(c.data(), f->cnt[f->ccur], sizeof(int32_t) * (size_t)f->n,
+                                hipMemcpyDeviceToHost, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int slam_fs_destroy(slam_fs* f) {
     if (!f) return SLAM_OK;
@@ -321,6 +465,12 @@ int slam_fs_destroy(slam_fs* f) {
     if (f->list_dev) (void)hipFree(f->list_dev);
     if (f->obs_dev) (void)hipFree(f->obs_dev);
     if (f->stage) (void)hipFree(f->stage);
+    for (int k = 0; k < 2; ++k)
+        if (f->cnt[k]) (void)hipFree(f->cnt[k]);
+    if (f->stamp) (void)hipFree(f->stamp);
+    if (f->bcnt) (void)hipFree(f->bcnt);
+    if (f->assoc_dev) (void)hipFree(f->assoc_dev);
+    if (f->cmax_pin) (void)hipHostFree(f->cmax_pin);
     for (auto& pr : f->ev)
         for (auto& ev : pr)
             if (ev) (void)hipEventDestroy(ev);
@@ -333,7 +483,15 @@ int slam_fs_info(slam_fs* f, int64_t* n_particles, int32_t* n_landmarks, int32_t
     SLAM_ARG_CHECK(f, "slam_fs_info: NULL handle");
     if (n_particles) *n_particles = f->n;
     if (n_landmarks) *n_landmarks = f->nl;
-    if (n_seen) *n_seen = (int32_t)std::count(f->seen.begin(), f->seen.end(), 1);
+    if (n_seen && f->assoc) {
+        SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+        std::vector<int32_t> c;
+        int rc = fs_counts_host(f, c);
+        if (rc) return rc;
+        *n_seen = *std::max_element(c.begin(), c.end());
+    } else if (n_seen) {
+        *n_seen = (int32_t)std::count(f->seen.begin(), f->seen.end(), 1);
+    }
     return SLAM_OK;
 }
 
@@ -355,9 +513,11 @@ int slam_fs_set_resample_next(slam_fs* f, int32_t on) {
 
 int slam_fs_set_maps(slam_fs* f, const int32_t* seen, const double* mean, const double* cov) {
     SLAM_ARG_CHECK(f, "slam_fs_set_maps: NULL handle");
-    SLAM_ARG_CHECK(seen && mean && cov, "slam_fs_set_maps: NULL argument");
+    SLAM_ARG_CHECK((seen || f->assoc) && mean && cov, "slam_fs_set_maps: NULL argument");
     slam_pf* h = f->pf;
     SLAM_HIP_TRY(hipSetDevice(h->device));
+    // an associating handle ignores seen: every slot is taken, the counts say which hold
+    if (f->assoc) return fs_maps_io(f, true, const_cast<double*>(mean), const_cast<double*>(cov));
     for (int32_t j = 0; j < f->nl; ++j) f->seen[(size_t)j] = seen[j] ? 1 : 0;
     SLAM_HIP_TRY(hipMemcpyAsync(f->seen_dev, f->seen.data(), sizeof(int32_t) * (size_t)f->nl,
                                 hipMemcpyHostToDevice, h->stream));
@@ -367,7 +527,15 @@ int slam_fs_set_maps(slam_fs* f, const int32_t* seen, const double* mean, const 
 int slam_fs_get_maps(slam_fs* f, int32_t* seen, double* mean, double* cov) {
     SLAM_ARG_CHECK(f, "slam_fs_get_maps: NULL handle");
     SLAM_HIP_TRY(hipSetDevice(f->pf->device));
-    if (seen) std::copy(f->seen.begin(), f->seen.end(), seen);
+    if (seen && f->assoc) {
+        std::vector<int32_t> c;
+        int rc = fs_counts_host(f, c);
+        if (rc) return rc;
+        const int32_t cm = *std::max_element(c.begin(), c.end());
+        for (int32_t j = 0; j < f->nl; ++j) seen[j] = j < cm;
+    } else if (seen) {
+        std::copy(f->seen.begin(), f->seen.end(), seen);
+    }
     return fs_maps_io(f, false, mean, cov);
 }
 
@@ -376,7 +544,15 @@ int slam_fs_get_map(slam_fs* f, int64_t particle, int32_t* seen, double* mean, d
     SLAM_ARG_CHECK(particle >= 0 && particle < f->n, "slam_fs_get_map: no such particle");
     slam_pf* h = f->pf;
     SLAM_HIP_TRY(hipSetDevice(h->device));
-    if (seen) std::copy(f->seen.begin(), f->seen.end(), seen);
+    if (seen && f->assoc) {
+        int32_t cp = 0;
+        SLAM_HIP_TRY(hipMemcpyAsync(&cp, f->cnt[f->ccur] + particle, sizeof(int32_t),
+                                    hipMemcpyDeviceToHost, h->stream));
+        SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int32_t j = 0; j < f->nl; ++j) seen[j] = j < cp;
+    } else if (seen) {
+        std::copy(f->seen.begin(), f->seen.end(), seen);
+    }
     int rc = fs_reserve_stage(f, 5 * (int64_t)f->nl);
     if (rc) return rc;
     for (int pass = 0; pass < 2; ++pass) {
@@ -384,8 +560,13 @@ int slam_fs_get_map(slam_fs* f, int64_t particle, int32_t* seen, double* mean, d
         if (!host) continue;
         const int32_t comp0 = pass == 0 ? 0 : 2, ncomp = pass == 0 ? 2 : 3;
         double* st = f->stage + (pass == 0 ? 0 : 2 * (size_t)f->nl);
-        fs_map_pack_kernel<<<fs_grid(1, f->nl), kFsThreads, 0, h->stream>>>(
-            f->n, f->npad, f->nl, particle, 1, comp0, ncomp, f->seen_dev, f->map[f->mcur], st);
+        if (f->assoc)
+            fs_assoc_pack_kernel<<<fs_grid(1, f->nl), kFsThreads, 0, h->stream>>>(
+                f->n, f->npad, f->nl, particle, 1, comp0, ncomp, f->cnt[f->ccur], f->map[f->mcur],
+                st);
+        else
+            fs_map_pack_kernel<<<fs_grid(1, f->nl), kFsThreads, 0, h->stream>>>(
+                f->n, f->npad, f->nl, particle, 1, comp0, ncomp, f->seen_dev, f->map[f->mcur], st);
         SLAM_HIP_TRY(hipGetLastError());
         SLAM_HIP_TRY(hipMemcpyAsync(host, st, sizeof(double) * (size_t)f->nl * ncomp,
                                     hipMemcpyDeviceToHost, h->stream));
@@ -446,6 +627,11 @@ int slam_fs_update(slam_fs* f, int32_t k, const int64_t* ids, const double* obs,
     SLAM_HIP_TRY(hipSetDevice(h->device));
     if ((rc = fs_stage_step_obs(f, k, ids, obs))) return rc;
     if ((rc = fs_enqueue_update(f, k, f->obs_dev, 0))) return rc;
+    if (f->assoc) {
+        rc = sync_results(h, 0, 1, res);
+        fs_note_seen(f, k, f->obs_host.data());
+        return rc;
+    }
     fs_note_seen(f, k, f->obs_host.data());
     return sync_results(h, 0, 1, res);
 }
@@ -465,7 +651,8 @@ int slam_fs_load_observations(slam_fs* f, int32_t n_steps, const int32_t* counts
     }
     const int64_t total = off[(size_t)n_steps];
     f->obs_host.resize((size_t)total);
-    for (int64_t t = 0; t < total; ++t) f->obs_host[(size_t)t] = fs_make_obs(f, ids[t], obs + 3 * t);
+    for (int64_t t = 0; t < total; ++t)
+        f->obs_host[(size_t)t] = fs_make_obs(f, ids ? ids[t] : -1, obs + 3 * t);
     SLAM_HIP_TRY(hipSetDevice(f->pf->device));
     f->run_off.clear();
     if (total > 0) {
@@ -491,6 +678,46 @@ int slam_fs_run(slam_fs* f, int32_t first_step, int32_t n_steps, const double* c
                                        nullptr, std::nan(""), results ? results + s : nullptr);
         if (rc) return rc;
     }
+    return SLAM_OK;
+}
+
+int slam_fs_set_counts(slam_fs* f, const int32_t* counts) {
+    SLAM_ARG_CHECK(f && counts, "slam_fs_set_counts: NULL argument");
+    SLAM_ARG_CHECK(f->assoc, "slam_fs_set_counts: not an associating handle");
+    int32_t cm = 0;
+    for (int64_t p = 0; p < f->n; ++p) {
+        SLAM_ARG_CHECK(counts[p] >= 0 && counts[p] <= f->nl,
+                       "slam_fs_set_counts: need 0 <= count <= max_landmarks");
+        cm = std::max(cm, counts[p]);
+    }
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    SLAM_HIP_TRY(hipMemcpyAsync(f->cnt[f->ccur], counts, sizeof(int32_t) * (size_t)f->n,
+                                hipMemcpyHostToDevice, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    f->cmax = cm;
+    return SLAM_OK;
+}
+
+int slam_fs_get_counts(slam_fs* f, int32_t* counts) {
+    SLAM_ARG_CHECK(f && counts, "slam_fs_get_counts: NULL argument");
+    SLAM_ARG_CHECK(f->assoc, "slam_fs_get_counts: not an associating handle");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    SLAM_HIP_TRY(hipMemcpyAsync(counts, f->cnt[f->ccur], sizeof(int32_t) * (size_t)f->n,
+                                hipMemcpyDeviceToHost, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    return SLAM_OK;
+}
+
+int slam_fs_get_assoc(slam_fs* f, int32_t* out) {
+    SLAM_ARG_CHECK(f && out, "slam_fs_get_assoc: NULL argument");
+    SLAM_ARG_CHECK(f->assoc, "slam_fs_get_assoc: not an associating handle");
+    SLAM_ARG_CHECK(f->acfg.record, "slam_fs_get_assoc: the handle does not record (record = 0)");
+    if (f->assoc_k == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    SLAM_HIP_TRY(hipMemcpy2DAsync(out, sizeof(int32_t) * (size_t)f->n, f->assoc_dev,
+                                  sizeof(int32_t) * (size_t)f->npad, sizeof(int32_t) * (size_t)f->n,
+                                  (size_t)f->assoc_k, hipMemcpyDeviceToHost, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
     return SLAM_OK;
 }
 

@@ -27,6 +27,13 @@ with a scan sensor of 9 m range::
         est, cov, (seen, mean, mcov) = slam.step((v, w), noisy)
     print(est, mean[seen.astype(bool)])
     slam.close()
+
+A real range / bearing sensor does not know which landmark it saw.
+``FastSLAM(n_particles, capacity, association="ml")`` drops the ids: every
+particle matches an observation to the likeliest landmark of its own map, or
+starts a new one (``p_new``), and ``best_map()`` is the heaviest particle's
+``(seen, mean, cov)`` with ``seen[j] = j < count``.  ``step`` then also accepts
+``(None, obs)``.
 """
 from __future__ import annotations
 
@@ -40,7 +47,8 @@ def _split(observations):
     if isinstance(observations, tuple) and len(observations) == 2 and \
             not hasattr(observations[0], "getLandMarkId"):
         ids, obs = observations
-        return np.asarray(ids, dtype=np.int64).reshape(-1), np.asarray(obs, dtype=np.float64).reshape(-1, 3)
+        obs = np.asarray(obs, dtype=np.float64).reshape(-1, 3)
+        return (None if ids is None else np.asarray(ids, dtype=np.int64).reshape(-1)), obs
     obs_list = list(observations)
     ids = np.array([o.getLandMarkId() for o in obs_list], dtype=np.int64)
     obs = np.array([[o.getDist(), o.getDir(), o.getOrient()] for o in obs_list],
@@ -51,7 +59,9 @@ def _split(observations):
 class FastSLAM:
     """Keyword arguments are DeviceFastSLAM's (dt, q, alphas, x0, motion,
     noise=(r_dist, r_dir, r_orient), use_orient, ess_threshold, seed, device);
-    the measurement noise defaults to ScanSensor's (10 %, 3 deg, 3 deg)."""
+    the measurement noise defaults to ScanSensor's (10 %, 3 deg, 3 deg).
+    ``association="ml"``: ``n_landmarks`` is the capacity of a particle's map and
+    the observations' ids are dropped (also ``p_new``, ``record_assoc``)."""
 
     def __init__(self, n_particles, n_landmarks, **kw):
         self.dev = DeviceFastSLAM(n_particles, n_landmarks, **kw)
@@ -63,8 +73,14 @@ class FastSLAM:
         weighted particle covariance.  The motion noise and the resampling
         offset come from the device RNG unless given (as slam_pf_step)."""
         ids, obs = _split(observations)
+        if self.dev.association == "ml":
+            ids = None
         self.last = self.dev.step(control, ids, obs, noise, u_resample)
         return self.last["x_est"], self.last["cov"], self.dev.best_map()
+
+    def best_map(self):
+        """The heaviest particle's (seen, mean [NL][2], cov [NL][3])."""
+        return self.dev.best_map()
 
     def close(self):
         self.dev.close()

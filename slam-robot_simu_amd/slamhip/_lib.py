@@ -68,6 +68,13 @@ class FSConfig(C.Structure):
                 ("r_orient", C.c_double), ("use_orient", C.c_int32), ("pad0", C.c_int32)]
 
 
+class FSAssocConfig(C.Structure):
+    _fields_ = [("log_p_new", C.c_double), ("record", C.c_int32), ("pad0", C.c_int32)]
+
+
+FS_ASSOC_MAX_OBS = 4096     # SLAM_FS_ASSOC_MAX_OBS
+
+
 class GraphEdge(C.Structure):
     _fields_ = [("time_bfr", C.c_int64), ("pose_bfr", C.c_int64), ("time_aft", C.c_int64),
                 ("pose_aft", C.c_int64), ("obs_bfr", C.c_double * 3), ("obs_aft", C.c_double * 3)]
@@ -210,6 +217,11 @@ SIGNATURES = {
     "slam_fs_load_observations": (C.c_int, [_P, C.c_int32, _I32, _I64, _D]),
     "slam_fs_run": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.POINTER(PFResult)]),
     "slam_fs_timing": (C.c_int, [_P, _D]),
+    "slam_fs_create_assoc": (C.c_int, [C.POINTER(FSConfig), C.POINTER(FSAssocConfig), C.c_int64,
+                                       C.c_int32, C.c_int, C.POINTER(_P)]),
+    "slam_fs_set_counts": (C.c_int, [_P, _I32]),
+    "slam_fs_get_counts": (C.c_int, [_P, _I32]),
+    "slam_fs_get_assoc": (C.c_int, [_P, _I32]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

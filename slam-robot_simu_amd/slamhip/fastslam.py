@@ -1,5 +1,6 @@
-"""Device FastSLAM 1.0 (known data association): a handle on libslam_hip's
-slam_fs_* entry points.
+"""Device FastSLAM 1.0 (known data association, or per-particle
+maximum-likelihood association): a handle on libslam_hip's slam_fs_* entry
+points.
 
 Every particle carries a pose, a weight and one 2-D EKF (mean, symmetric 2 x 2
 covariance) per landmark, resident in HBM; a step observes any subset of the
@@ -8,6 +9,11 @@ landmarks as (range, bearing, orientation) triples with their ids -- what
 single particle filter's (slamhip.pf); the per-particle map update with its
 log-domain weights and the resampling gather of whole maps are this handle's
 own kernels (csrc/fastslam.inl).
+
+With ``association="ml"`` the observations carry no ids: every particle scores
+an observation against the landmarks of its own map, takes the likeliest (or
+starts a new landmark when none reaches ``p_new``), and ``n_landmarks`` is the
+capacity of every particle's map (include/slam_hip.h states the contract).
 """
 from __future__ import annotations
 
@@ -16,11 +22,18 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FSConfig, PFResult, check, dptr
+from ._lib import FSAssocConfig, FSConfig, PFResult, check, dptr
 from .pf import DeviceParticleFilter, RunResults, _f64, make_config
 
 
+# The likelihood below which an observation starts a new landmark
+# (association="ml"); chosen by the sweep recorded in DESIGN 11c.
+P_NEW_DEFAULT = 1e-4
+
+
 def _ids_obs(ids, obs):
+    if ids is None:
+        return None, np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 3)
     ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
     obs = np.ascontiguousarray(obs, dtype=np.float64).reshape(-1, 3)
     if obs.shape[0] != ids.size:
@@ -28,19 +41,30 @@ def _ids_obs(ids, obs):
     return ids, obs
 
 
+def _iptr(ids):
+    return None if ids is None else ids.ctypes.data_as(_lib._I64)
+
+
 class DeviceFastSLAM:
     """Particles with per-particle landmark maps on one GPU.
 
     ``noise`` = (r_dist, r_dir, r_orient): ScanSensor's range noise fraction and
-    its bearing / orientation sigmas (rad).  The other keywords are
-    DeviceParticleFilter's."""
+    its bearing / orientation sigmas (rad).  ``association``: "known" (ids with
+    every observation) or "ml" (per-particle maximum likelihood: ``ids`` is
+    None everywhere, ``n_landmarks`` is the capacity of a particle's map,
+    ``p_new`` the likelihood below which an observation starts a new landmark,
+    ``record_assoc`` keeps each update's choices for ``last_assoc``).  The
+    other keywords are DeviceParticleFilter's."""
 
     ESS_CONFIRM_BAND = DeviceParticleFilter.ESS_CONFIRM_BAND
 
     def __init__(self, n_particles, n_landmarks, *, dt=0.1, q=None, alphas=(0.1,) * 6,
                  x0=(10.0, 0.0, np.pi / 2), motion="linear",
                  noise=(0.1, np.deg2rad(3.0), np.deg2rad(3.0)), use_orient=True,
-                 ess_threshold=None, seed=0, device=0):
+                 ess_threshold=None, seed=0, device=0, association="known",
+                 p_new=P_NEW_DEFAULT, record_assoc=False):
+        if association not in ("known", "ml"):
+            raise ValueError("association: 'known' or 'ml'")
         lib = _lib.load()
         self.n = int(n_particles)
         self.nl = int(n_landmarks)
@@ -51,14 +75,26 @@ class DeviceFastSLAM:
         cfg.use_orient = int(bool(use_orient))
         self.cfg = cfg
         self.motion = motion
+        self.association = association
+        self.record_assoc = bool(record_assoc)
+        self._last_k = 0
         h = C.c_void_p()
-        check(lib.slam_fs_create(C.byref(cfg), self.n, self.nl, int(device), C.byref(h)),
-              "slam_fs_create")
+        if association == "ml":
+            if not p_new > 0:
+                raise ValueError("p_new must be positive")
+            acfg = FSAssocConfig(float(np.log(p_new)), int(self.record_assoc), 0)
+            self.acfg = acfg
+            check(lib.slam_fs_create_assoc(C.byref(cfg), C.byref(acfg), self.n, self.nl, int(device),
+                                           C.byref(h)), "slam_fs_create_assoc")
+        else:
+            check(lib.slam_fs_create(C.byref(cfg), self.n, self.nl, int(device), C.byref(h)),
+                  "slam_fs_create")
         self._h = h
         self._lib = lib
         self.resample_next = False
         self.last = None
         self._run_steps = 0
+        self._run_counts = np.zeros(0, dtype=np.int32)
 
     # ------------------------------------------------------------ lifetime
     def close(self):
@@ -102,7 +138,11 @@ class DeviceFastSLAM:
         self.resample_next = bool(on)
 
     def set_maps(self, seen, mean, cov):
-        """seen [NL], mean [NP][NL][2], cov [NP][NL][3] (pxx, pxy, pyy)."""
+        """seen [NL], mean [NP][NL][2], cov [NP][NL][3] (pxx, pxy, pyy).
+        association="ml": ``seen`` is ignored (None will do); the counts say
+        which slots hold (``set_counts``)."""
+        if seen is None:
+            seen = np.zeros(self.nl, dtype=np.int32)
         seen = np.ascontiguousarray(seen, dtype=np.int32).reshape(self.nl)
         mean = _f64(mean, (self.n, self.nl, 2))
         cov = _f64(cov, (self.n, self.nl, 3))
@@ -126,6 +166,26 @@ class DeviceFastSLAM:
         check(self._lib.slam_fs_get_map(self._h, int(particle), seen.ctypes.data_as(_lib._I32),
                                         dptr(mean), dptr(cov)), "slam_fs_get_map")
         return seen, mean, cov
+
+    def set_counts(self, counts):
+        """association="ml": the landmarks each particle holds, [NP] in [0, n_landmarks]."""
+        c = np.ascontiguousarray(counts, dtype=np.int32).reshape(self.n)
+        check(self._lib.slam_fs_set_counts(self._h, c.ctypes.data_as(_lib._I32)),
+              "slam_fs_set_counts")
+
+    def get_counts(self):
+        c = np.empty(self.n, dtype=np.int32)
+        check(self._lib.slam_fs_get_counts(self._h, c.ctypes.data_as(_lib._I32)),
+              "slam_fs_get_counts")
+        return c
+
+    def last_assoc(self):
+        """association="ml", record_assoc=True: the last update's choices,
+        [k][NP]: the slot matched, -1 a new landmark, -2 dropped (map full)."""
+        a = np.empty((self._last_k, self.n), dtype=np.int32)
+        check(self._lib.slam_fs_get_assoc(self._h, a.ctypes.data_as(_lib._I32)),
+              "slam_fs_get_assoc")
+        return a
 
     def best_map(self):
         """The map estimate: the map of the last step's heaviest particle, as
@@ -163,9 +223,9 @@ class DeviceFastSLAM:
         ids, obs = _ids_obs(ids, obs)
         nz = None if noise is None else _f64(noise, (self.n, 3))
         res = PFResult()
-        check(self._lib.slam_fs_step(self._h, dptr(ctl), ids.size, ids.ctypes.data_as(_lib._I64),
-                                     dptr(obs), dptr(nz), float(u_resample), C.byref(res)),
-              "slam_fs_step")
+        check(self._lib.slam_fs_step(self._h, dptr(ctl), obs.shape[0], _iptr(ids), dptr(obs),
+                                     dptr(nz), float(u_resample), C.byref(res)), "slam_fs_step")
+        self._last_k = obs.shape[0]
         return self._finish(res)
 
     def resample(self, u_resample=float("nan"), force=False):
@@ -184,22 +244,29 @@ class DeviceFastSLAM:
     def update(self, ids, obs):
         ids, obs = _ids_obs(ids, obs)
         res = PFResult()
-        check(self._lib.slam_fs_update(self._h, ids.size, ids.ctypes.data_as(_lib._I64), dptr(obs),
-                                       C.byref(res)), "slam_fs_update")
+        check(self._lib.slam_fs_update(self._h, obs.shape[0], _iptr(ids), dptr(obs), C.byref(res)),
+              "slam_fs_update")
+        self._last_k = obs.shape[0]
         return self._finish(res)
 
     # ------------------------------------------------------- multi-step run
     def load_observations(self, steps):
         """steps: a sequence of (ids, obs) per step, uploaded once."""
         pairs = [_ids_obs(i, o) for i, o in steps]
-        counts = np.array([i.size for i, _ in pairs], dtype=np.int32)
-        ids = np.ascontiguousarray(np.concatenate([i for i, _ in pairs] + [np.zeros(0, np.int64)]))
+        counts = np.array([o.shape[0] for _, o in pairs], dtype=np.int32)
+        if any(i is None for i, _ in pairs):
+            if not all(i is None for i, _ in pairs):
+                raise ValueError("ids: None for every step or for none")
+            ids = None
+        else:
+            ids = np.ascontiguousarray(np.concatenate([i for i, _ in pairs] + [np.zeros(0, np.int64)]))
         obs = np.ascontiguousarray(np.concatenate([o for _, o in pairs] + [np.zeros((0, 3))]))
         check(self._lib.slam_fs_load_observations(self._h, len(pairs),
                                                   counts.ctypes.data_as(_lib._I32),
-                                                  ids.ctypes.data_as(_lib._I64), dptr(obs)),
+                                                  _iptr(ids), dptr(obs)),
               "slam_fs_load_observations")
         self._run_steps = len(pairs)
+        self._run_counts = counts
 
     def run(self, first_step, controls):
         """Steps [first_step, first_step + len(controls)) of the loaded
@@ -209,6 +276,7 @@ class DeviceFastSLAM:
         res = (PFResult * k)()
         check(self._lib.slam_fs_run(self._h, int(first_step), k, dptr(controls), res), "slam_fs_run")
         self.resample_next = bool(res[k - 1].resample_next)
+        self._last_k = int(self._run_counts[int(first_step) + k - 1])
         self.last = DeviceParticleFilter._res(res[k - 1])
         return RunResults(res)
 
