@@ -96,7 +96,8 @@ int slam_pf_get_state(slam_pf* h, double* x, double* y, double* th, double* w);
  * :234; = slam_pf_result.weight_sum of that step; 1 after set_state / resample).
  * The current weights are w_un / s (:235, NaN -> 1/NP).  Either pointer may be
  * NULL.  Lets a caller pin the step-end np.sum and the reductions against
- * numpy on the device's own w_un.  Single-GPU (deferred) handles. */
+ * numpy on the device's own w_un.  Every handle keeps its weights in this
+ * form (a shard: its local w_un). */
 int slam_pf_get_weights_raw(slam_pf* h, double* w_un, double* s);
 
 /* One estimator step of main_pf (particle_filter.py:102-117):

@@ -383,7 +383,7 @@ int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, 
     pc.r_cov[1] = pc.r_cov[2] = 0.0;
     pc.likelihood = SLAM_LIK_PRODUCT;       // zero landmarks: the factor is exactly 1
     slam_pf* pf = nullptr;
-    int rc = create_impl(&pc, n_particles, n_particles, 0, 0, nullptr, device, &pf, true, false);
+    int rc = create_impl(&pc, n_particles, n_particles, 0, 0, nullptr, device, &pf, false);
     if (rc) return rc;
     slam_fs* f = new slam_fs();
     f->cfg = *cfg;

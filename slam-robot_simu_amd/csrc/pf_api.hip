@@ -65,7 +65,7 @@ struct slam_pf {
     double *w = nullptr, *w_un = nullptr;
     // exact cumsum scratch
     double* c = nullptr;
-    uint64_t* kincl = nullptr;
+    uint64_t* kincl = nullptr;      // kincl, fexcl, spec_in: dist shards only (else null)
     int32_t* fexcl = nullptr;
     int32_t* idx = nullptr;
     int32_t nb_scan = 0;
@@ -86,12 +86,10 @@ struct slam_pf {
     int32_t* tail_leaves = nullptr;
     int32_t* tail_ops = nullptr;
     int32_t n_tail_leaves = 0, n_tail_ops = 0;
-    int32_t nb_norm = 0;
-    BlockPartial* bp = nullptr;
     double* wsum = nullptr;
     double* refp = nullptr;
     int32_t* flags = nullptr;
-    unsigned* tk = nullptr;         // ticket blocks: +0 np.sum, +1 normalize, +2 scans (x kTicketWords)
+    unsigned* tk = nullptr;         // ticket blocks: +0 np.sum, +2 scans (x kTicketWords)
     // inputs / step context
     double* lm = nullptr;
     double* noise = nullptr;
@@ -116,11 +114,10 @@ struct slam_pf {
     hipGraphExec_t graph[kGraphLevels][2] = {};   // [log2 steps][ping-pong parity]
     Timer tm;
     double ofs_host = 0.0;          // pinned-free staging of one step's resample offset
-    // deferred normalisation (single-GPU handles): current weights = w_un / s_cur
-    bool deferred = false;
+    // deferred normalisation: current weights = w_un / s_cur
+    double* s_cur = nullptr;
     bool scan_merged = false;   // exact cumsum in one launch (co-resident grid)
     bool scan_merged_ok = false;  // the merged launch is allowed for this handle
-    double* s_cur = nullptr;
     DeferParts dp{};
     FinSlices fsl{};                      // NP > 2^20: the finalize's slice pre-pass (pf_finalize.inl)
     int32_t nb_part = 0;
@@ -298,15 +295,11 @@ int set_flag(slam_pf* h, int word, int32_t v) {
     return SLAM_OK;
 }
 
-// S1 stand-alone: 256-block totals of w and their prefix (normalize_kernel
-// leaves the same arrays behind whenever the next step resamples).
+// S1 stand-alone: fused-block totals of w and their prefix (the step end
+// leaves the same prefix behind whenever the next step resamples).
 int launch_bsum(slam_pf* h) {
-    if (h->deferred)
-        scan_bsum256_kernel<<<h->nb_part, kPartPer, 0, h->stream>>>(
-            h->w_un, h->s_cur, h->pc.np_recip, h->n, h->bsum, h->boff, h->tk + 2 * kTicketWords);
-    else
-        scan_bsum_kernel<<<h->nb_norm, kNormThreads, 0, h->stream>>>(h->w, h->n, h->bsum, h->boff,
-                                                                      h->tk + 2 * kTicketWords);
+    scan_bsum256_kernel<<<h->nb_part, kPartPer, 0, h->stream>>>(
+        h->w_un, h->s_cur, h->pc.np_recip, h->n, h->bsum, h->boff, h->tk + 2 * kTicketWords);
     SLAM_HIP_TRY(hipGetLastError());
     return SLAM_OK;
 }
@@ -322,8 +315,8 @@ int launch_scans(slam_pf* h, int32_t force, bool with_s1) {
         const int rc = launch_bsum(h);
         if (rc) return rc;
     }
-    if (h->deferred && h->scan_merged) {
-        unsigned* tk = h->tk + 2 * kTicketWords;
+    unsigned* tk = h->tk + 2 * kTicketWords;
+    if (h->scan_merged) {
         scan_lean_merged_kernel<<<nb, kScanThreads, 0, s>>>(
             h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->stage, h->bk, h->bf, h->boffk,
             h->bofff, h->ktot, h->nspec, tk, h->flags, force, h->spec_out, h->c, step_io(h), h->pc,
@@ -332,32 +325,13 @@ int launch_scans(slam_pf* h, int32_t force, bool with_s1) {
         SLAM_HIP_TRY(hipGetLastError());
         return SLAM_OK;
     }
-    if (h->deferred) {
-        unsigned* tk = h->tk + 2 * kTicketWords;
-        scan_lean_classify_kernel<<<nb, kScanThreads, 0, s>>>(
-            h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->stage, h->bk, h->bf, h->boffk,
-            h->bofff, h->ktot, h->nspec, tk, h->flags, force, h->spec_out, h->c, h->nb_part);
-        scan_lean_expand_kernel<<<nb, kScanThreads, 0, s>>>(
-            h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->boffk, h->bofff, h->spec_out,
-            h->c, h->flags, force, step_io(h), h->pc, h->cfg.seed, h->dp.mark,
-            h->dp.carry, h->nb_part);
-        SLAM_HIP_TRY(hipGetLastError());
-        return SLAM_OK;
-    }
-    const double* w = h->deferred ? h->w_un : h->w;
-    const double* sd = h->deferred ? h->s_cur : nullptr;
-    const int32_t gran = h->deferred ? kPartPer : kNormPer;
-    scan_classify_kernel<<<nb, kScanThreads, 0, s>>>(
-        w, n, h->boff, nullptr, h->c, h->kincl, h->fexcl, h->bk, h->bf, h->boffk, h->bofff,
-        h->ktot, h->nspec, delta, 0, h->tk + 2 * kTicketWords, h->flags, force, sd,
-        h->pc.np_recip, gran);
-    scan_emit_kernel<<<nb, kScanThreads, 0, s>>>(w, n, h->c, h->kincl, h->fexcl, h->boffk,
-                                                 h->bofff, h->spec_in, 0, h->spec_out, h->nspec,
-                                                 h->ktot, 1, h->c, h->tk + 2 * kTicketWords, h->flags,
-                                                 force, sd, h->pc.np_recip);
-    scan_expand_kernel<<<nb, kScanThreads, 0, s>>>(n, h->kincl, h->fexcl, h->boffk, h->bofff,
-                                                   h->spec_out, h->c, h->flags, nullptr,
-                                                   nullptr, force);
+    scan_lean_classify_kernel<<<nb, kScanThreads, 0, s>>>(
+        h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->stage, h->bk, h->bf, h->boffk,
+        h->bofff, h->ktot, h->nspec, tk, h->flags, force, h->spec_out, h->c, h->nb_part);
+    scan_lean_expand_kernel<<<nb, kScanThreads, 0, s>>>(
+        h->w_un, h->s_cur, h->pc.np_recip, n, h->boff, delta, h->boffk, h->bofff, h->spec_out,
+        h->c, h->flags, force, step_io(h), h->pc, h->cfg.seed, h->dp.mark,
+        h->dp.carry, h->nb_part);
     SLAM_HIP_TRY(hipGetLastError());
     return SLAM_OK;
 }
@@ -366,26 +340,24 @@ int launch_fused(slam_pf* h, int motion, bool host_noise) {
     const int64_t n = h->n;
     const int src = h->cur, dst = 1 - h->cur;
     hipStream_t s = h->stream;
-    const unsigned g = h->deferred ? (unsigned)h->nb_part : grid_for(n, 256);
+    const unsigned g = (unsigned)h->nb_part;
     const int lik = h->cfg.likelihood;
     const StepIO io = step_io(h);
     tic(h, 0);
-    const double* w_in = h->deferred ? nullptr : h->w;     // deferred: read from w_un
     const double* nsrc = h->noise_src ? h->noise_src : h->noise;
-#define SLAM_FUSED_D(M, L, HN, D, WT)                                                            \
-    pf_fused_kernel<M, L, HN, D, WT><<<g, 256, 0, s>>>(n, h->x[src], h->y[src], h->th[src],     \
-                                                       h->x[dst], h->y[dst], h->th[dst], w_in,  \
-                                                       h->w_un, h->c, h->flags, nsrc, h->lm, io, \
-                                                       h->pc, h->lc, h->cfg.seed, h->s_cur,      \
-                                                       h->refp, h->dp)
-    // every handle is deferred; write-through pair stores while the launch's
-    // output (32 B per particle) fits the L2s, plain stores above
+#define SLAM_FUSED_D(M, L, HN, WT)                                                               \
+    pf_fused_kernel<M, L, HN, WT><<<g, 256, 0, s>>>(n, h->x[src], h->y[src], h->th[src],        \
+                                                    h->x[dst], h->y[dst], h->th[dst], h->w_un,   \
+                                                    h->c, h->flags, nsrc, h->lm, io, h->pc,      \
+                                                    h->lc, h->cfg.seed, h->s_cur, h->refp, h->dp)
+    // write-through pair stores while the launch's output (32 B per particle)
+    // fits the L2s, plain stores above
 #if SLAM_FUSED_WT == 1
     const bool wt = n <= SLAM_FUSED_WT_MAX;
 #define SLAM_FUSED(M, L, HN)                                                                     \
-    do { if (wt) SLAM_FUSED_D(M, L, HN, true, true); else SLAM_FUSED_D(M, L, HN, true, false); } while (0)
+    do { if (wt) SLAM_FUSED_D(M, L, HN, true); else SLAM_FUSED_D(M, L, HN, false); } while (0)
 #else
-#define SLAM_FUSED(M, L, HN) SLAM_FUSED_D(M, L, HN, true, SLAM_FUSED_WT == 2)
+#define SLAM_FUSED(M, L, HN) SLAM_FUSED_D(M, L, HN, SLAM_FUSED_WT == 2)
 #endif
     if (motion == kMotionNone) {
         if (lik == SLAM_LIK_PRODUCT) SLAM_FUSED(2, 0, false); else SLAM_FUSED(2, 1, false);
@@ -416,39 +388,18 @@ int launch_reduce(slam_pf* h, int32_t resampled_known) {
     hipStream_t s = h->stream;
     const int c = h->cur;
     tic(h, 1);
-    if (h->deferred) {
-        const bool sliced = h->fsl.nsl > 1;
-        if (!sliced || (h->fsl.nsl <= kFinFastSlices && n / kSumChunk <= 2048)) {
-            if (sliced)
-                finalize_slices_kernel<<<h->fsl.nsl - 1, kFinThreads, 0, s>>>(n, h->dp, h->fsl);
-            auto kern = sliced ? finalize_fast_kernel<true> : finalize_fast_kernel<false>;
-            kern<<<1, kFinThreads, 0, s>>>(
-                n, h->dp, h->w_un, h->s_cur, h->tail_leaves, h->tail_ops, h->n_tail_leaves,
-                h->n_tail_ops, h->x[c], h->y[c], h->th[c], h->refp, h->flags, h->cfg.ess_threshold,
-                step_io(h), resampled_known, h->pc.np_recip, h->boff, h->fsl);
-            toc(h, 1);
-            SLAM_HIP_TRY(hipGetLastError());
-            return SLAM_OK;
-        }
-        if (h->fsl.nsl > 1)
-            finalize_slices_kernel<<<h->fsl.nsl - 1, kFinThreads, 0, s>>>(n, h->dp, h->fsl);
-        finalize_deferred_kernel<<<1, kFinThreads, 0, s>>>(
-            n, h->dp, h->w_un, h->s_cur, h->tail_leaves, h->tail_ops, h->n_tail_leaves,
-            h->n_tail_ops, h->x[c], h->y[c], h->th[c], h->refp, h->flags, h->cfg.ess_threshold,
-            step_io(h), resampled_known, h->pc.np_recip, h->boff, h->fsl);
-        toc(h, 1);
-        SLAM_HIP_TRY(hipGetLastError());
-        return SLAM_OK;
-    }
-    chunk_sum_kernel<<<h->nchunks, 512, 0, s>>>(h->w_un, n, h->part, h->tail_leaves, h->tail_ops,
-                                                 h->n_tail_leaves, h->n_tail_ops, h->tk,
-                                                 h->wsum);
-    normalize_kernel<<<h->nb_norm, kNormThreads, 0, s>>>(n, h->w_un, h->w, h->wsum,
-                                                          h->pc.np_recip, h->x[c], h->y[c],
-                                                          h->th[c], h->refp, h->bp, h->bsum, 0);
-    finalize_kernel<<<1, 1024, 0, s>>>(h->bp, h->nb_norm, h->bsum, h->boff, h->x[c], h->y[c],
-                                        h->th[c], h->refp, h->wsum, h->flags,
-                                        h->cfg.ess_threshold, step_io(h), resampled_known, 0);
+    // up to 2^20 particles one block holds every fused block's partials in
+    // registers; above, a slice pre-pass reduces them first, and the fast
+    // kernel takes what it can still hold (pf_finalize.inl)
+    const bool sliced = h->fsl.nsl > 1;
+    if (sliced) finalize_slices_kernel<<<h->fsl.nsl - 1, kFinThreads, 0, s>>>(n, h->dp, h->fsl);
+    auto kern = !sliced ? finalize_fast_kernel<false>
+                : (h->fsl.nsl <= kFinFastSlices && n / kSumChunk <= 2048) ? finalize_fast_kernel<true>
+                                                                          : finalize_general_kernel;
+    kern<<<1, kFinThreads, 0, s>>>(
+        n, h->dp, h->w_un, h->s_cur, h->tail_leaves, h->tail_ops, h->n_tail_leaves,
+        h->n_tail_ops, h->x[c], h->y[c], h->th[c], h->refp, h->flags, h->cfg.ess_threshold,
+        step_io(h), resampled_known, h->pc.np_recip, h->boff, h->fsl);
     toc(h, 1);
     SLAM_HIP_TRY(hipGetLastError());
     return SLAM_OK;
@@ -553,7 +504,7 @@ int launch_run_setup(slam_pf* h, int32_t first_step, int32_t n_steps, const doub
     const bool formed = h->prep_step == first_step && h->prep_ctl[0] == controls[0] &&
                         h->prep_ctl[1] == controls[1];
     const int32_t next = first_step + n_steps;
-    const bool guess = prep_next && h->deferred && !h->mt && h->lc.closed && next < h->cap;
+    const bool guess = prep_next && !h->mt && h->lc.closed && next < h->cap;
     h->prep_step = -1;                      // (re)armed by the caller once the batch succeeded
     if (prep_next) *prep_next = guess ? next : -1;
     int32_t ncopy = n_steps;
@@ -643,8 +594,8 @@ int launch_step(slam_pf* h, bool host_noise) {
 }
 
 // The records of steps [first, first + count) from the coherent host buffer:
-// stored there by the batch's last step end (exported: slam_pf_run on a
-// deferred handle) or by one export launch here.
+// stored there by the batch's last step end (exported: slam_pf_run) or by
+// one export launch here.
 int sync_results(slam_pf* h, int32_t first, int32_t count, slam_pf_result* out, bool exported = false) {
     static_assert(sizeof(slam_pf_result) % 8 == 0, "result records move as 8-byte words");
     if (!exported) {
@@ -680,7 +631,7 @@ int sync_results(slam_pf* h, int32_t first, int32_t count, slam_pf_result* out, 
 
 int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, int64_t gbase,
                 int32_t n_landmarks, const double* landmarks, int device, slam_pf** out,
-                bool deferred, bool dist_shard) {
+                bool dist_shard) {
     SLAM_ARG_CHECK(cfg && out, "slam_pf_create: NULL argument");
     SLAM_ARG_CHECK(n_local > 0 && n_global < (int64_t(1) << 31) && gbase >= 0 &&
                        gbase + n_local <= n_global,
@@ -712,9 +663,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     const int64_t n = n_local;
     h->nb_scan = (int32_t)((n + kScanBlock - 1) / kScanBlock);
     h->nchunks = (int32_t)((n + kSumChunk - 1) / kSumChunk);
-    h->nb_norm = (int32_t)((n + kNormPer - 1) / kNormPer);
     h->nb_part = (int32_t)((n + kPartPer - 1) / kPartPer);
-    h->deferred = deferred;
     {
         // merged exact-cumsum launch only when its whole grid is co-resident
         // (its blocks wait for the last one); otherwise two launches
@@ -723,7 +672,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
                                                          kScanThreads, 0) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) ==
                 hipSuccess)
-            h->scan_merged_ok = deferred && (int64_t)h->nb_scan <= (int64_t)per_cu * cus / 2;
+            h->scan_merged_ok = (int64_t)h->nb_scan <= (int64_t)per_cu * cus / 2;
         h->scan_merged = h->scan_merged_ok;
     }
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -736,11 +685,11 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
         slam_pf_destroy(h);                               \
         return rc;                                        \
     }
-    // deferred handles: particle and weight arrays padded to whole fused blocks
-    // (the fused kernel moves particle pairs with 16-byte loads and stores)
-    // (a sharded handle: npad staging slots on either side of each particle
-    // array for the particles a resample receives from other ranks, DeferParts.goff)
-    const int64_t npad = deferred ? (int64_t)h->nb_part * kPartPer : n;
+    // particle and weight arrays padded to whole fused blocks (the fused
+    // kernel moves particle pairs with 16-byte loads and stores); a sharded
+    // handle: npad staging slots on either side of each particle array for the
+    // particles a resample receives from other ranks (DeferParts.goff)
+    const int64_t npad = (int64_t)h->nb_part * kPartPer;
     const int64_t side = dist_shard ? npad : 0;
     for (int k = 0; k < 2; ++k) {
         A(h->x[k], npad + 2 * side);
@@ -761,11 +710,9 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     A(h->w_un, npad);
     if (npad > n) SLAM_HIP_TRY(hipMemsetAsync(h->w_un, 0, sizeof(double) * npad, h->stream));
     A(h->c, npad);
-    A(h->kincl, n);
-    A(h->fexcl, n);
     A(h->idx, n);
-    A(h->bsum, std::max(h->nb_norm, h->nb_part));
-    A(h->boff, std::max(h->nb_norm, h->nb_part) + 1);
+    A(h->bsum, h->nb_part);
+    A(h->boff, h->nb_part + 1);
     A(h->s_cur, 1);
     A(h->dp.pmax, h->nb_part + 1);                        // + 1: the finalize's pair loads
     A(h->dp.pidx, h->nb_part);
@@ -775,7 +722,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     A(h->dp.leaf, (size_t)(kPartPer / 128) * h->nb_part);
     A(h->dp.mark, npad);
     A(h->dp.carry, h->nb_part + 1);
-    if (deferred && h->nb_part > kFinThreads * kFinRegBlocks) {
+    if (h->nb_part > kFinThreads * kFinRegBlocks) {
         const int32_t per = kFinThreads * kFinRegBlocks;
         h->fsl.nsl = (h->nb_part + per - 1) / per;
         A(h->fsl.m, h->fsl.nsl);
@@ -789,7 +736,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     }
     SLAM_HIP_TRY(hipMemsetAsync(h->dp.mark, 0xff, sizeof(int64_t) * npad, h->stream));
     SLAM_HIP_TRY(hipMemsetAsync(h->dp.carry, 0, sizeof(int32_t) * (h->nb_part + 1), h->stream));
-    // tile totals: 2048-element tiles (shards) or 512-element wave tiles (deferred)
+    // tile totals: 2048-element tiles (the sharded exchange) or 512-element wave tiles
     const int32_t ntile_max = std::max(h->nb_scan, h->nb_part);
     A(h->bk, ntile_max);
     A(h->boffk, ntile_max);
@@ -797,8 +744,14 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     A(h->bofff, ntile_max);
     A(h->ktot, 1);
     A(h->nspec, 1);
-    A(h->spec_in, n);
-    if (deferred) A(h->stage, n);
+    if (dist_shard) {
+        // per-element scratch of the sharded exchange's exact cumsum (the
+        // launches in pf_dist_api.inl; slam_dist_create takes dist shards only)
+        A(h->kincl, n);
+        A(h->fexcl, n);
+        A(h->spec_in, n);
+    }
+    A(h->stage, n);
     A(h->spec_out, n);
     if (h->scan_merged_ok) {
         A(h->hand, (size_t)(h->nb_scan + kHandReplicas) * kHandGranules);
@@ -808,7 +761,6 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
         SLAM_HIP_TRY(hipMemsetAsync(h->spec_tag, 0, sizeof(uint64_t) * n * kSpecGranules, h->stream));
     }
     A(h->part, h->nchunks);
-    A(h->bp, h->nb_norm);
     A(h->wsum, 1);
     // [0..2] last estimate, [4..6] the one before, [7] moves of the first
     // expansion reference (closed_prep_reference)
@@ -860,9 +812,8 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     return SLAM_OK;
 }
 
-// deferred path: h->w <- w_un / s_cur (the current normalised weights)
+// h->w <- w_un / s_cur (the current normalised weights)
 int materialize_w(slam_pf* h) {
-    if (!h->deferred) return SLAM_OK;
     normalize_only_kernel<<<grid_for(h->n, 256), 256, 0, h->stream>>>(h->n, h->w_un, h->s_cur,
                                                                        h->pc.np_recip, h->w);
     SLAM_HIP_TRY(hipGetLastError());
@@ -871,9 +822,7 @@ int materialize_w(slam_pf* h) {
 
 int set_s_one(slam_pf* h) {
     static const double one = 1.0;
-    if (h->deferred)
-        SLAM_HIP_TRY(hipMemcpyAsync(h->s_cur, &one, sizeof(double), hipMemcpyHostToDevice,
-                                    h->stream));
+    SLAM_HIP_TRY(hipMemcpyAsync(h->s_cur, &one, sizeof(double), hipMemcpyHostToDevice, h->stream));
     return SLAM_OK;
 }
 
@@ -932,8 +881,7 @@ extern "C" {
 
 int slam_pf_create(const slam_pf_config* cfg, int64_t n_particles, int32_t n_landmarks,
                    const double* landmarks, int device, slam_pf** out) {
-    return create_impl(cfg, n_particles, n_particles, 0, n_landmarks, landmarks, device, out, true,
-                       false);
+    return create_impl(cfg, n_particles, n_particles, 0, n_landmarks, landmarks, device, out, false);
 }
 
 int slam_pf_destroy(slam_pf* h) {
@@ -995,22 +943,16 @@ int slam_pf_set_state(slam_pf* h, const double* x, const double* y, const double
     if (y) SLAM_HIP_TRY(hipMemcpyAsync(h->y[c], y, b, hipMemcpyHostToDevice, h->stream));
     if (th) SLAM_HIP_TRY(hipMemcpyAsync(h->th[c], th, b, hipMemcpyHostToDevice, h->stream));
     if (w) {
-        if (h->deferred) {
-            static const double one = 1.0;
-            SLAM_HIP_TRY(hipMemcpyAsync(h->w_un, w, b, hipMemcpyHostToDevice, h->stream));
-            SLAM_HIP_TRY(hipMemcpyAsync(h->s_cur, &one, sizeof(double), hipMemcpyHostToDevice,
-                                        h->stream));
-        } else {
-            SLAM_HIP_TRY(hipMemcpyAsync(h->w, w, b, hipMemcpyHostToDevice, h->stream));
-        }
+        SLAM_HIP_TRY(hipMemcpyAsync(h->w_un, w, b, hipMemcpyHostToDevice, h->stream));
+        int rc = set_s_one(h);
+        if (rc) return rc;
         // particle_filter.py:210-211: the resample decision from these weights
         // (single GPU; a shard's caller decides from the global ESS)
         if (h->n == h->n_global) {
             double s2 = 0.0;
             for (int64_t i = 0; i < h->n; ++i) s2 += w[i] * w[i];
             h->resample_next = (1.0 / s2 < h->cfg.ess_threshold) ? 1 : 0;
-            int rc = set_flag(h, kFlagResample, h->resample_next);
-            if (rc) return rc;
+            if ((rc = set_flag(h, kFlagResample, h->resample_next))) return rc;
         }
     }
     SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1036,7 +978,6 @@ int slam_pf_get_state(slam_pf* h, double* x, double* y, double* th, double* w) {
 
 int slam_pf_get_weights_raw(slam_pf* h, double* w_un, double* s) {
     SLAM_ARG_CHECK(h, "slam_pf_get_weights_raw: NULL handle");
-    SLAM_ARG_CHECK(h->deferred, "slam_pf_get_weights_raw: not a deferred (single-GPU) handle");
     SLAM_HIP_TRY(hipSetDevice(h->device));
     if (w_un)
         SLAM_HIP_TRY(hipMemcpyAsync(w_un, h->w_un, h->n * sizeof(double), hipMemcpyDeviceToHost,
@@ -1102,7 +1043,7 @@ int slam_pf_resample(slam_pf* h, double u_resample, int32_t force, int32_t* resa
     const int src = h->cur, dst = 1 - h->cur;
     gather_kernel<<<grid_for(h->n, 256), 256, 0, h->stream>>>(
         h->n, h->idx, h->x[src], h->y[src], h->th[src], h->x[dst], h->y[dst], h->th[dst],
-        h->deferred ? h->w_un : h->w, h->pc.np_recip);
+        h->w_un, h->pc.np_recip);
     SLAM_HIP_TRY(hipGetLastError());
     if ((rc = set_s_one(h))) return rc;
     h->cur = dst;
@@ -1161,11 +1102,7 @@ int slam_pf_predict(slam_pf* h, const double* control, const double* noise) {
     h->lc.nl = nl;
     h->lc.neg_nl_ln_den = lnd;
     if (rc) return rc;
-    if (h->deferred) {
-        if ((rc = set_s_one(h))) return rc;   // w_un now holds the normalised weights
-    } else {
-        SLAM_HIP_TRY(hipMemcpyAsync(h->w, h->w_un, h->n * 8, hipMemcpyDeviceToDevice, h->stream));
-    }
+    if ((rc = set_s_one(h))) return rc;   // w_un now holds the normalised weights
     if ((rc = set_flag(h, kFlagResample, h->resample_next))) return rc;
     h->stepno++;
     SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1276,7 +1213,7 @@ int slam_pf_run(slam_pf* h, int32_t first_step, int32_t n_steps, const double* c
             h->stepno++;
         }
     }
-    rc = sync_results(h, first_step, n_steps, results, h->deferred);
+    rc = sync_results(h, first_step, n_steps, results, true);
     if (rc == SLAM_OK && prep_next >= 0) {
         h->prep_step = prep_next;
         h->prep_ctl[0] = controls[2 * (n_steps - 1)];

@@ -1101,7 +1101,7 @@ __global__ __launch_bounds__(kScanThreads) void dist_resample_merged_kernel(
 // ---------------------------------------------------------------- record
 // The shard's reduction record from the fused kernel's block partials,
 // pushed into every peer's G1 slot (parity = epoch & 1), then kXG1.  One
-// workgroup of kFinThreads lanes, laid out like finalize_deferred_kernel:
+// workgroup of kFinThreads lanes, laid out like finalize_general_kernel:
 // every lane issues the loads of its blocks and leaves first; the sums are
 // wave butterflies (a fixed order); the tie-window candidates are the first
 // kDistWin blocks whose max is within 2^-48 of M, found in parallel (the
@@ -1130,7 +1130,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     double pm[kFinRegBlocks], q[kFinRegBlocks][11];
     bool has[kFinRegBlocks];
 #pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {     // neighbour pairs (finalize_deferred_kernel)
+    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {     // neighbour pairs (finalize_general_kernel)
         const int64_t b = fin_blk(tid, 2 * kp);
         has[2 * kp] = b < nb;
         has[2 * kp + 1] = b + 1 < nb;

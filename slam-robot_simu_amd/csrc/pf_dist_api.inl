@@ -362,7 +362,7 @@ int slam_pf_create_dist_shard(const slam_pf_config* cfg, int64_t n_local, int64_
                    "slam_pf_create_dist_shard: every shard but the last must hold a multiple of "
                    "8192 particles (np.sum buffer alignment)");
     SLAM_ARG_CHECK(n_local <= (int64_t)2048 * kSumChunk, "slam_pf_create_dist_shard: n_local > 2^24");
-    return create_impl(cfg, n_local, n_global, gbase, n_landmarks, landmarks, device, out, true, true);
+    return create_impl(cfg, n_local, n_global, gbase, n_landmarks, landmarks, device, out, true);
 }
 
 // the standard split of N particles over `world` ranks: rank r holds
@@ -389,7 +389,7 @@ int slam_dist_create(slam_pf** shards, int32_t n_held, int32_t world, int32_t ra
     *out = nullptr;
     const int64_t N = shards[0]->n_global;
     for (int i = 0; i < n_held; ++i) {
-        SLAM_ARG_CHECK(shards[i] && shards[i]->deferred && shards[i]->n_global == N,
+        SLAM_ARG_CHECK(shards[i] && shards[i]->n_global == N,
                        "slam_dist_create: shards must come from slam_pf_create_dist_shard, same filter");
         // the resample gathers address the staging slots either side of the
         // particle arrays (goff = npad), which only a dist shard has

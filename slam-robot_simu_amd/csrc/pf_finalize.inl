@@ -40,8 +40,6 @@ constexpr int kFinLeafLanes = 4;            // lanes per 8192-element buffer (16
 constexpr int kFinBufPerRound = kFinThreads / kFinLeafLanes;   // 128 buffers per round
 constexpr int kFinCand = 8;                 // argmax candidate records staged in LDS
 constexpr int kFinBatch = 8;                // loads in flight per lane beyond the registers (NP > 2^20)
-constexpr int kFinSumBatch = 2;             // blocks (12 loads each) in flight in the sums pass
-constexpr int kFinPrefixRounds = 32;        // the next step's block prefix in registers (NP <= 2^23)
 
 struct FinRecord {
     double pre, xe[3];
@@ -335,59 +333,6 @@ __device__ void fin_next_prefix(const int64_t n, const int64_t nb, const bool ok
             }
         }
         if (tid == 0) boff[nb] = tot[0] + tot[1];
-    } else if (ok && (nb + kFinWaves * 64 - 1) / (kFinWaves * 64) <= kFinPrefixRounds) {
-        // NP <= 2^23 (round 6: the batched form below took 39 us at 2^23): wave
-        // w takes the contiguous blocks [w R 64, (w+1) R 64) in R rounds of 64
-        // (lane l: block w R 64 + 64 r + l, coalesced), every load issued
-        // first; inclusive wave scans carry the running total over the rounds,
-        // then the waves' totals in order
-        const int R = (int)((nb + kFinWaves * 64 - 1) / (kFinWaves * 64));
-        const int64_t wb0 = (int64_t)wave * R * 64;
-        double pv[kFinPrefixRounds], qv[kFinPrefixRounds];
-#pragma unroll
-        for (int r = 0; r < kFinPrefixRounds; ++r) {
-            if (r < R) {
-                const int64_t b = wb0 + 64 * r + lane;
-                const int64_t bb = b < nb ? b : 0;
-                pv[r] = dp.pmax[bb];
-                qv[r] = dp.ps[0][bb];
-            }
-        }
-        // the rounds' scans are independent (interleaved by the scheduler); the
-        // running total over the rounds is added after
-        double ex[kFinPrefixRounds], rt[kFinPrefixRounds];
-#pragma unroll
-        for (int r = 0; r < kFinPrefixRounds; ++r) {
-            if (r < R) {
-                const int64_t b = wb0 + 64 * r + lane;
-                const double t = b < nb ? (pv[r] / s) * qv[r] : 0.0;
-                ex[r] = wave_excl_scan_rows(t, rt[r]);
-            }
-        }
-        double run = 0.0;
-#pragma unroll
-        for (int r = 0; r < kFinPrefixRounds; ++r) {
-            if (r < R) {
-                ex[r] = run + ex[r];
-                run = run + rt[r];
-            }
-        }
-        if (lane == 0) scr[wave] = run;
-        __syncthreads();
-        double base = 0.0, all = 0.0;
-#pragma unroll
-        for (int w = 0; w < kFinWaves; ++w) {
-            if (w < wave) base = base + scr[w];
-            all = all + scr[w];
-        }
-#pragma unroll
-        for (int r = 0; r < kFinPrefixRounds; ++r) {
-            if (r < R) {
-                const int64_t b = wb0 + 64 * r + lane;
-                if (b < nb) boff[b] = base + ex[r];
-            }
-        }
-        if (tid == 0) boff[nb] = all;
     } else {
         // fused-block totals of w for the next step's exact cumsum (S1), moved
         // through LDS so that lane t owns the contiguous blocks [t per, (t+1) per)
@@ -443,7 +388,14 @@ __device__ void fin_next_prefix(const int64_t n, const int64_t nb, const bool ok
     }
 }
 
-__global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
+// The general step end: any number of slices and buffers (the fast kernel
+// below takes what fits its registers and LDS; launch_reduce chooses).
+// Requires the slice pre-pass: it is launched only behind
+// finalize_slices_kernel (sl.nsl > 1, so NP > 2^20 and at least one full round
+// of kFinBufPerRound np.sum buffers).  The workgroup reduces slice 0 (the
+// first 2048 fused blocks) from its registers and takes every later slice's
+// max, sums and buffer values from the pre-pass.
+__global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     const int64_t n, const DeferParts dp, const double* __restrict__ w_un,
     double* __restrict__ s_cur, const int32_t* __restrict__ tail_leaves,
     const int32_t* __restrict__ tail_ops, const int32_t n_tail_leaves, const int32_t n_tail_ops,
@@ -501,10 +453,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
         }
     }
     const int part = tid & (kFinLeafLanes - 1);
-    double L[4];                                   // fused-block subtree sums
+    double L[4];                                   // fused-block subtree sums (buffer tid / 4 < nfull)
     {
-        const int64_t c = tid / kFinLeafLanes;
-        const double* Lp = dp.leaf + 16 * (c < nfull ? c : 0) + 4 * part;
+        const double* Lp = dp.leaf + 16 * (int64_t)(tid / kFinLeafLanes) + 4 * part;
 #pragma unroll
         for (int j = 0; j < 4; ++j) L[j] = Lp[j];
     }
@@ -514,23 +465,6 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
 #pragma unroll
     for (int k = 0; k < kFinRegBlocks; ++k)
         if (has[k]) mlane = fmax(mlane, pm[k]);
-    // NP > 2^20: blocks beyond the registers (two passes: max, then sums)
-    // (round 5: every loop over the blocks beyond the registers issues a batch
-    // of loads before it uses them -- one memory round trip per iteration made
-    // the 2^23-particle finalize 50-110 us; the adds keep their order)
-    const int64_t bx0 = tid + (int64_t)kFinThreads * kFinRegBlocks;
-    const bool sliced = sl.nsl > 1;                  // blocks beyond the registers pre-reduced
-    const int64_t bxs = sliced ? nb : bx0;           // (the loops below then do nothing)
-    for (int64_t b0 = bxs; b0 < nb; b0 += kFinBatch * (int64_t)kFinThreads) {
-        double v[kFinBatch];
-#pragma unroll
-        for (int u = 0; u < kFinBatch; ++u) {
-            const int64_t b = b0 + (int64_t)u * kFinThreads;
-            v[u] = (b < nb) ? dp.pmax[b] : -1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < kFinBatch; ++u) mlane = fmax(mlane, v[u]);
-    }
     double acc[11];
 #pragma unroll
     for (int j = 0; j < 11; ++j) acc[j] = 0.0;
@@ -546,46 +480,15 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
                 for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
             }
         }
-        for (int64_t b0 = bxs; b0 < nb; b0 += kFinSumBatch * (int64_t)kFinThreads) {
-            double pv[kFinSumBatch], qv[kFinSumBatch][11];
-#pragma unroll
-            for (int u = 0; u < kFinSumBatch; ++u) {
-                const int64_t b = b0 + (int64_t)u * kFinThreads;
-                const int64_t bb = (b < nb) ? b : b0;
-                pv[u] = dp.pmax[bb];
-#pragma unroll
-                for (int j = 0; j < 11; ++j) qv[u][j] = dp.ps[j][bb];
-            }
-#pragma unroll
-            for (int u = 0; u < kFinSumBatch; ++u) {
-                if (b0 + (int64_t)u * kFinThreads < nb) {
-                    const double r = pv[u] * rm;
-                    acc[0] += r * qv[u][0];
-                    acc[1] += (r * r) * qv[u][1];
-#pragma unroll
-                    for (int j = 2; j < 11; ++j) acc[j] += r * qv[u][j];
-                }
-            }
-        }
     }
     const double mx = wave_max_f64(mlane);
     if (lane == 0) s_wmax[wave] = mx;
-    // ---- np.sum: 8192-element buffers, 128 per round, pairwise inside
-    // (sliced: only the first slice's round here, the slices' buffer values after)
+    // ---- np.sum: 8192-element buffers, pairwise inside; slice 0's round of
+    // kFinBufPerRound buffers from the leaves here (every lane has one: nfull >=
+    // kFinBufPerRound), the later slices' buffer values after
     double s = 0.0;
-    const int64_t nleaf = sliced ? (nfull < kFinBufPerRound ? nfull : kFinBufPerRound) : nfull;
-    for (int64_t c0 = 0; c0 < nleaf; c0 += kFinBufPerRound) {
-        const int64_t cnt = (nfull - c0 < kFinBufPerRound) ? nfull - c0 : kFinBufPerRound;
-        const int64_t c = c0 + tid / kFinLeafLanes;
-        double v = 0.0;
-        if (tid / kFinLeafLanes < cnt) {
-            if (c0 > 0) {
-                const double* Lp = dp.leaf + 16 * c + 4 * part;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) L[j] = Lp[j];
-            }
-            v = (L[0] + L[1]) + (L[2] + L[3]);
-        }
+    {
+        double v = (L[0] + L[1]) + (L[2] + L[3]);
         static_assert(kFinLeafLanes == 4, "two quad swaps");
         {
             const double o = dpp_f64<kDppXor1>(v);
@@ -595,30 +498,26 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
             const double o = dpp_f64<kDppXor2>(v);
             v = (part & 2) ? (o + v) : (v + o);
         }
-        if (c0 > 0) __syncthreads();                     // lane 0 is done with the previous round
-        if (part == 0 && tid / kFinLeafLanes < cnt) sh[tid / kFinLeafLanes] = v;
+        if (part == 0) sh[tid / kFinLeafLanes] = v;
         __syncthreads();
-        if (c0 + kFinBufPerRound < nfull && tid == 0) {  // not the last round: fold it now
-            s = lds_chain_sum(s, sh, (int)cnt);
+        if (kFinBufPerRound < nfull && tid == 0) {       // not the last round: fold it now
+            s = lds_chain_sum(s, sh, kFinBufPerRound);
         }
     }
-    if (nfull == 0) __syncthreads();                     // s_wmax visible
-    int64_t last_cnt = nfull - ((nfull - 1) / kFinBufPerRound) * kFinBufPerRound;
-    if (sliced && nfull > kFinBufPerRound) {
-        // the slices' buffer values, staged 2048 at a time behind the chain so far
-        for (int64_t c0 = kFinBufPerRound; c0 < nfull; c0 += 2048) {
-            const int64_t cnt = (nfull - c0 < 2048) ? nfull - c0 : 2048;
-            __syncthreads();                                  // lane 0 is done with sh
-            for (int64_t k = tid; k < cnt; k += kFinThreads) sh[k] = sl.buf[c0 + k];
-            __syncthreads();
-            if (c0 + 2048 < nfull && tid == 0) s = lds_chain_sum(s, sh, (int)cnt);
-            last_cnt = cnt;
-        }
+    int64_t last_cnt = kFinBufPerRound;
+    // the slices' buffer values, staged 2048 at a time behind the chain so far
+    for (int64_t c0 = kFinBufPerRound; c0 < nfull; c0 += 2048) {
+        const int64_t cnt = (nfull - c0 < 2048) ? nfull - c0 : 2048;
+        __syncthreads();                                  // lane 0 is done with sh
+        for (int64_t k = tid; k < cnt; k += kFinThreads) sh[k] = sl.buf[c0 + k];
+        __syncthreads();
+        if (c0 + 2048 < nfull && tid == 0) s = lds_chain_sum(s, sh, (int)cnt);
+        last_cnt = cnt;
     }
     double M = s_wmax[0];
 #pragma unroll
     for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
-    if (sliced) {                                        // the slices' maxima (every wave alike)
+    {                                                    // the slices' maxima (every wave alike)
         double msl = -1.0;
         for (int g = 1 + lane; g < sl.nsl; g += 64) msl = fmax(msl, sl.m[g]);
         M = fmax(M, wave_max_f64(msl));
@@ -628,8 +527,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
         // the last round's buffers left to right (the other waves meanwhile
         // rescale their partials and fetch the argmax candidates)
         __builtin_amdgcn_s_setprio(3);
-        if (nfull > 0)
-            s = lds_chain_sum(s, sh, (int)last_cnt);
+        s = lds_chain_sum(s, sh, (int)last_cnt);
         __builtin_amdgcn_s_setprio(0);
     }
     {
@@ -683,19 +581,17 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
             }
             if (lane == 0) s_tot[j] = r;
         }
-        if (sliced) {                                    // + the slices, rescaled to M, in order
-            __syncthreads();
-            if (tid < 11) {
-                double r = s_tot[tid];
-                for (int g = 1; g < sl.nsl; ++g) {
-                    const double mg = sl.m[g];
-                    if (mg > 0.0) {
-                        const double f = mg / M;
-                        r = r + sl.q[(int64_t)g * 11 + tid] * (tid == 1 ? f * f : f);
-                    }
+        __syncthreads();                                 // + the slices, rescaled to M, in order
+        if (tid < 11) {
+            double r = s_tot[tid];
+            for (int g = 1; g < sl.nsl; ++g) {
+                const double mg = sl.m[g];
+                if (mg > 0.0) {
+                    const double f = mg / M;
+                    r = r + sl.q[(int64_t)g * 11 + tid] * (tid == 1 ? f * f : f);
                 }
-                s_tot[tid] = r;
             }
+            s_tot[tid] = r;
         }
         // ---- argmax: the first block whose max rounds to fl(M / s)
         const double mval = M / s;
@@ -704,6 +600,10 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
         for (int k = kFinRegBlocks - 1; k >= 0; --k)
             if (has[k] && pm[k] >= M * (1.0 - 0x1p-48) && pm[k] / s == mval)
                 cb = (unsigned long long)fin_blk(tid, k);
+        // the blocks beyond the registers: a batch of loads issued before they
+        // are used (one memory round trip per iteration made the 2^23-particle
+        // step end 50-110 us)
+        const int64_t bx0 = tid + (int64_t)kFinThreads * kFinRegBlocks;
         for (int64_t b0 = bx0; b0 < nb && cb == ~0ull; b0 += kFinBatch * (int64_t)kFinThreads) {
             double v[kFinBatch];
 #pragma unroll
@@ -816,7 +716,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_deferred_kernel(
 
 // ---------------------------------------------------------------------------
 // NP <= 2^24 (round 6): the same work as
-// finalize_deferred_kernel in an order built around its latencies (phase
+// finalize_general_kernel in an order built around its latencies (phase
 // probe).  The leaves are requested first, so np.sum's buffer chain
 // starts on lane 0 after one round trip and runs while the block partials are
 // still arriving; each wave requests the argmax records of its own candidate

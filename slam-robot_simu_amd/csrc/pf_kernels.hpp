@@ -33,16 +33,13 @@ constexpr int kSumChunk = 8192;     // np.sum buffer size (particle_filter.py:23
 constexpr int kScanBlock = 2048;    // elements per block of the exact-cumsum passes
 constexpr int kScanThreads = 256;
 constexpr int kScanPer = kScanBlock / kScanThreads;  // 8
-constexpr int kNormThreads = 256;
-constexpr int kNormEPT = 4;                          // particles per lane in normalize
-constexpr int kNormPer = kNormThreads * kNormEPT;    // particles per normalize block
 #ifndef SLAM_DEFER_PPT
 #define SLAM_DEFER_PPT 2
 #endif
-constexpr int kDeferPPT = SLAM_DEFER_PPT;            // particles per lane, deferred fused kernel
-constexpr int kPartPer = 256 * kDeferPPT;            // particles per fused block (deferred path)
+constexpr int kDeferPPT = SLAM_DEFER_PPT;            // particles per lane of the fused kernel
+constexpr int kPartPer = 256 * kDeferPPT;            // particles per fused block
 
-// Deferred normalisation (single-GPU handles): the fused kernel leaves, per
+// Deferred normalisation (every handle): the fused kernel leaves, per
 // kPartPer-particle block, its max unnormalised weight M_b with the first index,
 // sums scaled by 1/M_b (sum u, sum u^2, sum u d, sum u d d^T with u = w_un/M_b
 // and d = particle - refp; scaling keeps squares of tiny likelihoods out of
@@ -103,7 +100,7 @@ struct PredictConst {
 };
 
 // Device-resident per-step inputs/outputs of a loaded batch.  Kernels read the
-// step index from ctr[0] (advanced by the last block of normalize_kernel), so
+// step index from ctr[0] (advanced by the step end, pf_finalize.inl), so
 // one captured step graph replays unchanged for every step.
 struct StepIO {
     const double* ctl;      // [cap][2] control (v, omega)

@@ -5,13 +5,14 @@
 namespace slam {
 
 
-// The fused step kernel: [resample gather +] predict + likelihood + weight.
-// DEFER = false (shards): one particle per lane, previous weights normalised
-// in w_in.  DEFER = true (single GPU, gbase = 0, particle arrays padded to
-// whole blocks): lane t of block b holds the consecutive particles
-// b kPartPer + kDeferPPT t + k -- 16-byte loads and stores, one device-RNG
-// pair per lane -- and the previous weights are w_un / s (read and rewritten
-// in place), followed by the block epilogue that replaces the normalise pass.
+// The fused step kernel: [resample gather +] predict + likelihood + weight,
+// for single-GPU handles and shards alike.  The particle arrays are padded to
+// whole blocks and a handle's first particle has an even global index: lane t
+// of block b holds the consecutive particles b kPartPer + kDeferPPT t + k --
+// 16-byte loads and stores, one device-RNG pair per particle pair.  The
+// previous weights are w_un / s (deferred normalisation: w_un is read and
+// rewritten in place), and the block epilogue leaves the partials the step
+// end reduces, so that no pass over the particles normalises.
 // Four waves per SIMD (<= 128 VGPRs): the log-sum kernel's slow-path product
 // would otherwise push it to 129 and three waves.
 #ifndef SLAM_FUSED_WPE
@@ -24,19 +25,19 @@ namespace slam {
 #endif
 // One fused block's tile (blk: 256 lanes x P particles): the body of
 // pf_fused_kernel (a persistent grid walking tiles measured slower: DESIGN 4.4).
-template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER, bool WT>
+template <int MOTION, int LIK, bool HOSTNOISE, bool WT>
 __device__ __forceinline__ void pf_fused_tile(
     const int64_t blk, const int32_t st, const uint32_t rstep, const int32_t rflag,
     const double* __restrict__ zs, const int wave_s, const RngTabs& rtab,
     const int64_t n, const double* __restrict__ xs, const double* __restrict__ ys,
     const double* __restrict__ ts, double* __restrict__ xo, double* __restrict__ yo,
-    double* __restrict__ to, const double* __restrict__ w_in, double* __restrict__ w_un,
+    double* __restrict__ to, double* __restrict__ w_un,
     const double* __restrict__ c, int32_t* __restrict__ flags, const double* __restrict__ noise,
     const double* __restrict__ lm, const StepIO& io, const PredictConst& pc, const LikConst& lc,
     const uint64_t seed, const double* __restrict__ s_in, const double* __restrict__ refp,
     const DeferParts& dp) {
-    constexpr int P = DEFER ? kDeferPPT : 1;
-    // the deferred path's pair stores: write-through (WT: st_wt_pair), so
+    constexpr int P = kDeferPPT;
+    // the pair stores: write-through (WT: st_wt_pair), so
     // that the launch leaves none of its 32 B per particle dirty in L2 for the
     // kernel's end to write back, or plain.  A template flag and not a branch:
     // the compiler takes the asm store for a write to any address and turns
@@ -61,35 +62,32 @@ __device__ __forceinline__ void pf_fused_tile(
     //      under the device RNG below; the weights are consumed at the end
     double wprev[P];
     double lx[P], ly[P], lt[P];
-    if (DEFER) {
+#pragma unroll
+    for (int h = 0; h < P; h += 2) {
+        const double2 wu = *reinterpret_cast<const double2*>(w_un + i0 + h);
+        wprev[h] = wu.x;
+        wprev[h + 1] = wu.y;
+    }
+    if (rflag != 1) {
 #pragma unroll
         for (int h = 0; h < P; h += 2) {
-            const double2 wu = *reinterpret_cast<const double2*>(w_un + i0 + h);
-            wprev[h] = wu.x;
-            wprev[h + 1] = wu.y;
+            const double2 a = *reinterpret_cast<const double2*>(xs + i0 + h);
+            const double2 b = *reinterpret_cast<const double2*>(ys + i0 + h);
+            const double2 c2 = *reinterpret_cast<const double2*>(ts + i0 + h);
+            lx[h] = a.x;
+            lx[h + 1] = a.y;
+            ly[h] = b.x;
+            ly[h + 1] = b.y;
+            lt[h] = c2.x;
+            lt[h + 1] = c2.y;
         }
-        if (rflag != 1) {
-#pragma unroll
-            for (int h = 0; h < P; h += 2) {
-                const double2 a = *reinterpret_cast<const double2*>(xs + i0 + h);
-                const double2 b = *reinterpret_cast<const double2*>(ys + i0 + h);
-                const double2 c2 = *reinterpret_cast<const double2*>(ts + i0 + h);
-                lx[h] = a.x;
-                lx[h + 1] = a.y;
-                ly[h] = b.x;
-                ly[h + 1] = b.y;
-                lt[h] = c2.x;
-                lt[h + 1] = c2.y;
-            }
-        }
-    } else {
-        wprev[0] = w_in[idx[0]];
     }
     // host / pre-drawn noise of the lane's particles (particle-major [n][3]):
-    // three 16-byte loads per pair, issued with the others
+    // three 16-byte loads per pair, issued with the others; the ragged last
+    // block's lanes past n read particle n - 1's (idx[])
     double gn[P][3];
     if (HOSTNOISE && MOTION != kMotionNone) {
-        if (DEFER && i0 + P <= n) {
+        if (i0 + P <= n) {
 #pragma unroll
             for (int h = 0; h < P; h += 2) {
                 const double2* q2 = reinterpret_cast<const double2*>(noise + 3 * (i0 + h));
@@ -112,7 +110,7 @@ __device__ __forceinline__ void pf_fused_tile(
     // ---- source particles: the resample gather (rflag 1: search the exact
     //      cumsum here; 2: already gathered) or the particles themselves
     double x[P], y[P], th[P];
-    if (DEFER && rflag == 1 && !flags[kFlagFallback]) {
+    if (rflag == 1 && !flags[kFlagFallback]) {
         // the expand pass's inverse map: run starts in mark[], the block's
         // first source in carry[]; a running max over the block's positions
         __shared__ int32_t s_wmax[4];
@@ -174,17 +172,13 @@ __device__ __forceinline__ void pf_fused_tile(
             y[k] = ys[src];
             th[k] = ts[src];
         }
-    } else if (DEFER) {
+    } else {
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             x[k] = lx[k];
             y[k] = ly[k];
             th[k] = lt[k];
         }
-    } else {
-        x[0] = xs[idx[0]];
-        y[0] = ys[idx[0]];
-        th[0] = ts[idx[0]];
     }
 
     // ---- standard normals of the motion noise
@@ -200,22 +194,15 @@ __device__ __forceinline__ void pf_fused_tile(
     } else {
         const uint64_t gi = (uint64_t)(pc.gbase + i0);
         double h[6];
-        if (DEFER) {                                          // gi even: whole pairs
 #pragma unroll
-            for (int pr = 0; pr < P / 2; ++pr) {
+        for (int pr = 0; pr < P / 2; ++pr) {                  // gi even: whole pairs
 #ifdef SLAM_PROBE_NO_RNG                                      // instruction-count probe only
-                for (int j = 0; j < 6; ++j) h[j] = 0.0;
+            for (int j = 0; j < 6; ++j) h[j] = 0.0;
 #else
-                pair_normals((gi >> 1) + pr, rstep, seed, rtab, h);
+            pair_normals((gi >> 1) + pr, rstep, seed, rtab, h);
 #endif
 #pragma unroll
-                for (int j = 0; j < 6; ++j) g[2 * pr + j / 3][j % 3] = h[j];
-            }
-        } else {
-            pair_normals(gi >> 1, rstep, seed, rtab, h);
-            const bool odd = gi & 1;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) g[0][j] = odd ? h[3 + j] : h[j];
+            for (int j = 0; j < 6; ++j) g[2 * pr + j / 3][j % 3] = h[j];
         }
         if (MOTION == SLAM_MOTION_LINEAR) {                   // noise_j = sum_k g_k q[k][j]
 #pragma unroll
@@ -242,29 +229,23 @@ __device__ __forceinline__ void pf_fused_tile(
     // loads, and the wait for those is a wait for the stores before them (one
     // in-order counter) -- the drain this path is meant to avoid
     constexpr bool kLate = WT && LIK != SLAM_LIK_PRODUCT;
-    if (DEFER) {
-        if constexpr (!kLate) {
+    if constexpr (!kLate) {
 #pragma unroll
-            for (int h = 0; h < P; h += 2) {
-                st_pair(xo + i0 + h, xv[h], xv[h + 1]);
-                st_pair(yo + i0 + h, yv[h], yv[h + 1]);
-                st_pair(to + i0 + h, tv[h], tv[h + 1]);
-            }
+        for (int h = 0; h < P; h += 2) {
+            st_pair(xo + i0 + h, xv[h], xv[h + 1]);
+            st_pair(yo + i0 + h, yv[h], yv[h + 1]);
+            st_pair(to + i0 + h, tv[h], tv[h + 1]);
         }
-    } else if (valid[0]) {
-        xo[i0] = xv[0];
-        yo[i0] = yv[0];
-        to[i0] = tv[0];
     }
 
     FPROBE(3, xv[P - 1] + sp[P - 1]);
     // previous weights: particle_filter.py:222 (a resampled step starts from
-    // 1/NP) / :235-236 (deferred: w_un / s, NaN -> 1/NP)
+    // 1/NP) / :235-236 (w_un / s, NaN -> 1/NP)
     double pw[P];
-    const double s_prev = DEFER ? *s_in : 1.0;
+    const double s_prev = *s_in;
 #pragma unroll
     for (int k = 0; k < P; ++k)
-        pw[k] = rflag ? pc.np_recip : (DEFER ? norm_w(wprev[k], s_prev, pc.np_recip) : wprev[k]);
+        pw[k] = rflag ? pc.np_recip : norm_w(wprev[k], s_prev, pc.np_recip);
     // ---- likelihood and weight (particle_filter.py:170-198)
     double bn[P];
 #ifdef SLAM_PROBE_NO_LIK                                   // timing probe only: not exact
@@ -280,24 +261,20 @@ __device__ __forceinline__ void pf_fused_tile(
     double wv[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) wv[k] = valid[k] ? pw[k] * bn[k] : 0.0;   // particle_filter.py:194
-    if constexpr (DEFER) {
-        if constexpr (kLate) {
+    if constexpr (kLate) {
 #pragma unroll
-            for (int h = 0; h < P; h += 2) {
-                st_pair(xo + i0 + h, xv[h], xv[h + 1]);
-                st_pair(yo + i0 + h, yv[h], yv[h + 1]);
-                st_pair(to + i0 + h, tv[h], tv[h + 1]);
-            }
+        for (int h = 0; h < P; h += 2) {
+            st_pair(xo + i0 + h, xv[h], xv[h + 1]);
+            st_pair(yo + i0 + h, yv[h], yv[h + 1]);
+            st_pair(to + i0 + h, tv[h], tv[h + 1]);
         }
-#pragma unroll
-        for (int h = 0; h < P; h += 2) st_pair(w_un + i0 + h, wv[h], wv[h + 1]);
-#ifndef SLAM_NO_EPILOGUE
-        defer_epilogue(base, n, wv, xv, yv, tv, refp, dp, wave_s, (int)blk);
-#endif
-        FPROBE(5, wv[0]);
-    } else if (valid[0]) {
-        w_un[i0] = wv[0];
     }
+#pragma unroll
+    for (int h = 0; h < P; h += 2) st_pair(w_un + i0 + h, wv[h], wv[h + 1]);
+#ifndef SLAM_NO_EPILOGUE
+    defer_epilogue(base, n, wv, xv, yv, tv, refp, dp, wave_s, (int)blk);
+#endif
+    FPROBE(5, wv[0]);
 }
 
 // The step's first fused block, after its own particles: the NEXT step's
@@ -328,13 +305,13 @@ __device__ __forceinline__ void pf_fused_prep_next(const int32_t st, const int w
 #define SLAM_FUSED_PARAMS                                                                          \
     const int64_t n, const double* __restrict__ xs, const double* __restrict__ ys,                  \
         const double* __restrict__ ts, double* __restrict__ xo, double* __restrict__ yo,            \
-        double* __restrict__ to, const double* __restrict__ w_in, double* __restrict__ w_un,        \
+        double* __restrict__ to, double* __restrict__ w_un,                                         \
         const double* __restrict__ c, int32_t* __restrict__ flags,                                  \
         const double* __restrict__ noise, const double* __restrict__ lm, StepIO io,                 \
         PredictConst pc, LikConst lc, uint64_t seed, const double* __restrict__ s_in,               \
         const double* __restrict__ refp, DeferParts dp
-#define SLAM_FUSED_ARGS n, xs, ys, ts, xo, yo, to, w_in, w_un, c, flags, noise, lm, io, pc, lc, \
-                        seed, s_in, refp, dp
+#define SLAM_FUSED_ARGS n, xs, ys, ts, xo, yo, to, w_un, c, flags, noise, lm, io, pc, lc, seed, \
+                        s_in, refp, dp
 
 // The step's uniform inputs and the RNG tables (every lane reaches the barrier)
 #define SLAM_FUSED_PROLOGUE                                                                      \
@@ -351,14 +328,13 @@ __device__ __forceinline__ void pf_fused_prep_next(const int32_t st, const int w
         __syncthreads();                                                                         \
     }
 
-template <int MOTION, int LIK, bool HOSTNOISE, bool DEFER, bool WT>
+template <int MOTION, int LIK, bool HOSTNOISE, bool WT>
 __global__ __launch_bounds__(256) SLAM_FUSED_ATTR void pf_fused_kernel(SLAM_FUSED_PARAMS) {
-    static_assert(!DEFER || kDeferPPT % 2 == 0, "the deferred path moves particle pairs");
-    static_assert(DEFER || !WT, "write-through pair stores: the deferred path only");
+    static_assert(kDeferPPT % 2 == 0, "the fused kernel moves particle pairs");
     SLAM_FUSED_PROLOGUE
-    pf_fused_tile<MOTION, LIK, HOSTNOISE, DEFER, WT>(blockIdx.x, st, rstep, rflag, zs, wave_s, rtab,
-                                                 SLAM_FUSED_ARGS);
-    if constexpr (DEFER) pf_fused_prep_next<MOTION>(st, wave_s, lm, io, pc, lc, refp);
+    pf_fused_tile<MOTION, LIK, HOSTNOISE, WT>(blockIdx.x, st, rstep, rflag, zs, wave_s, rtab,
+                                              SLAM_FUSED_ARGS);
+    pf_fused_prep_next<MOTION>(st, wave_s, lm, io, pc, lc, refp);
 }
 
 // ====================================================================
@@ -622,8 +598,8 @@ __device__ __forceinline__ void block_scan_pair(const uint64_t* kin, uint64_t* k
 }
 
 // ====================================================================
-// normalise (particle_filter.py:226-237) + reductions; the last block
-// combines the block partials in block order and writes the step result.
+// reductions of the step end (particle_filter.py:226-237): block partials,
+// their fixed-order combination and the step's result record
 // ====================================================================
 __device__ __forceinline__ void bp_zero(BlockPartial& a) {
     a.maxv = -1.0;
@@ -686,48 +662,8 @@ __device__ __forceinline__ BlockPartial bp_block_reduce(BlockPartial a, BlockPar
     return r;
 }
 
-// result record from the combined partial (x_est = particle at the argmax)
-__device__ void write_result(const BlockPartial& r, const double* xs, const double* ys,
-                             const double* ts, const int64_t gbase, double* refp,
-                             const double s, int32_t* flags, const double ess_th,
-                             const double ess_band, slam_pf_result* res,
-                             const int32_t resampled_known) {
-    slam_pf_result o;
-    const int64_t mi = r.maxi;
-    o.max_idx = mi;
-    o.max_val = r.maxv;
-    o.x_est[0] = xs[mi - gbase];
-    o.x_est[1] = ys[mi - gbase];
-    o.x_est[2] = ts[mi - gbase];
-    const double inv = 1.0 / r.sw;
-    const double mu[3] = {r.m1[0] * inv, r.m1[1] * inv, r.m1[2] * inv};
-    const double m2[9] = {r.m2[0], r.m2[1], r.m2[2], r.m2[1], r.m2[3], r.m2[4], r.m2[2], r.m2[4], r.m2[5]};
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) o.cov[3 * a + b] = m2[3 * a + b] * inv - mu[a] * mu[b];
-    o.ess = 1.0 / r.sw2;
-    o.weight_sum = s;
-    o.resampled = resampled_known >= 0 ? resampled_known : (flags[kFlagResample] != 0);
-    o.resample_next = (o.ess < ess_th) ? 1 : 0;
-    o.ess_near = (fabs(o.ess - ess_th) <= ess_band * ess_th) ? 1 : 0;
-    o.status = flags[kFlagStatus];
-    o.n_special = flags[kFlagNSpecial];
-    o.dd_waves = flags[kFlagDDWaves];
-    flags[kFlagDDWaves] = 0;
-    flags[kFlagResample] = o.resample_next;
-    flags[kFlagMarkGen] = flags[kFlagMarkGen] + 1;
-    flags[kFlagStatus] = 0;
-    // the estimate, kept two steps deep as the expansion's reference
-    // (closed_prep_reference: the argmax particle is the same bits however
-    // the filter is sharded, which a summed mean would not be)
-    for (int k = 0; k < 3; ++k) {
-        refp[4 + k] = refp[k];
-        refp[k] = o.x_est[k];
-    }
-    refp[7] = 2.0;
-    *res = o;
-}
-
-// result record with x_est given (deferred path: taken from the block partials)
+// result record from the combined partial; x_est is given (the particle at
+// the argmax, taken from the fused blocks' partials)
 // The flag words the step's record reads (fetched early by the finalize, whose
 // record is on the step's critical path)
 struct FlagWords {
@@ -787,120 +723,6 @@ __device__ int32_t write_result_xe(const BlockPartial& r, const double* xe, doub
     const double rp[3] = {refp[0], refp[1], refp[2]};
     return write_result_fw(r, xe, refp, rp, s, flags, load_flag_words(flags), ess_th, ess_band, res,
                            resampled_known, res_host);
-}
-
-// One normalise block = kNormPer particles (kNormThreads lanes x kNormEPT,
-// coalesced per k); all loads of a lane are issued before any use.
-__global__ __launch_bounds__(kNormThreads) void normalize_kernel(
-    const int64_t n, const double* __restrict__ w_un, double* __restrict__ w,
-    const double* __restrict__ s_in, const double np_recip, const double* __restrict__ xs,
-    const double* __restrict__ ys, const double* __restrict__ ts, const double* __restrict__ refp,
-    BlockPartial* __restrict__ bp, double* __restrict__ bsum, const int64_t gbase) {
-    __shared__ BlockPartial shp[kNormThreads / 64];
-    const double s = *s_in;
-    const double r0 = refp[0], r1 = refp[1], r2 = refp[2];
-    const int64_t base = (int64_t)blockIdx.x * kNormPer + threadIdx.x;
-    double wu[kNormEPT], xv[kNormEPT], yv[kNormEPT], tv[kNormEPT];
-    if (base + (kNormEPT - 1) * kNormThreads < n) {
-#pragma unroll
-        for (int k = 0; k < kNormEPT; ++k) {
-            const int64_t i = base + k * kNormThreads;
-            wu[k] = w_un[i];
-            xv[k] = xs[i];
-            yv[k] = ys[i];
-            tv[k] = ts[i];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kNormEPT; ++k) {
-            const int64_t i = base + k * kNormThreads;
-            const bool ok = i < n;
-            wu[k] = ok ? w_un[i] : 0.0;
-            xv[k] = ok ? xs[i] : r0;
-            yv[k] = ok ? ys[i] : r1;
-            tv[k] = ok ? ts[i] : r2;
-        }
-    }
-    BlockPartial a;
-    bp_zero(a);
-#pragma unroll
-    for (int k = 0; k < kNormEPT; ++k) {
-        const int64_t i = base + k * kNormThreads;
-        if (i < n) {
-            double v = wu[k] / s;                        // particle_filter.py:235
-            if (isnan(v)) v = np_recip;                  // :236
-            w[i] = v;
-            if (v > a.maxv) {
-                a.maxv = v;
-                a.maxi = gbase + i;
-            }
-            a.sw += v;
-            a.sw2 += v * v;
-            const double d0 = xv[k] - r0, d1 = yv[k] - r1, d2 = tv[k] - r2;
-            const double v0 = v * d0, v1 = v * d1, v2 = v * d2;
-            a.m1[0] += v0;
-            a.m1[1] += v1;
-            a.m1[2] += v2;
-            a.m2[0] += v0 * d0;
-            a.m2[1] += v0 * d1;
-            a.m2[2] += v0 * d2;
-            a.m2[3] += v1 * d1;
-            a.m2[4] += v1 * d2;
-            a.m2[5] += v2 * d2;
-        }
-    }
-    const BlockPartial r = bp_block_reduce(a, shp);
-    if (threadIdx.x == 0) {
-        bp[blockIdx.x] = r;
-        bsum[blockIdx.x] = r.sw;                         // approximate block total (S1)
-    }
-}
-
-// Combine the normalise blocks' partials in block order (one block of up to
-// 1024 lanes, one partial per lane, then a fixed tree), write the step's
-// result record, advance the step context, and -- when the next step
-// resamples -- scan the block totals for its exact cumsum.  A separate launch
-// instead of a last-arriver tail: the kernel boundary costs less than the
-// serial ticket/load chain of an in-kernel combine.
-__global__ __launch_bounds__(1024) void finalize_kernel(
-    const BlockPartial* __restrict__ bp, const int32_t nb, const double* __restrict__ bsum,
-    double* __restrict__ boff, const double* __restrict__ xs, const double* __restrict__ ys,
-    const double* __restrict__ ts, double* __restrict__ refp, const double* __restrict__ s_in,
-    int32_t* __restrict__ flags, const double ess_th, StepIO io, const int32_t resampled_known,
-    const int64_t gbase) {
-    __shared__ BlockPartial shp[1024 / 64];
-    __shared__ double shd[1024 / 64 + 1];
-    __shared__ int32_t want_scan;
-    BlockPartial c;
-    bp_zero(c);
-    for (int k = threadIdx.x; k < nb; k += blockDim.x) bp_merge(c, bp[k]);
-    const BlockPartial tot = bp_block_reduce(c, shp);
-    if (threadIdx.x == 0) {
-        const int32_t st = io.ctr[0];
-        write_result(tot, xs, ys, ts, gbase, refp, *s_in, flags, ess_th, io.ess_band, io.res + st,
-                     resampled_known);
-        want_scan = flags[kFlagResample];
-        io.ctr[0] = st + 1;                              // advance the step context
-        io.ctr[1] = io.ctr[1] + 1;
-    }
-    __syncthreads();
-    if (want_scan) {
-        // exclusive prefix of the block totals (plain loads: previous kernel's data)
-        const int per = (nb + 1023) / 1024;
-        const int b0 = threadIdx.x * per;
-        double loc = 0.0;
-        for (int k = 0; k < per; ++k)
-            if (b0 + k < nb) loc += bsum[b0 + k];
-        double total;
-        double ex = block_excl_scan<double, 1024>(loc, shd, total);
-        for (int k = 0; k < per; ++k)
-            if (b0 + k < nb) {
-                const double v = bsum[b0 + k];
-                boff[b0 + k] = ex;
-                ex = ex + v;
-            }
-        if (threadIdx.x == 0) boff[nb] = total;
-    }
 }
 
 // np.sum of one full 8192-element buffer from its 64 leaf sums (perfect
@@ -973,7 +795,7 @@ __global__ __launch_bounds__(256) void normalize_only_kernel(const int64_t n,
     if (i < n) w[i] = norm_w(w_un[i], *s, np_recip);
 }
 
-// S1 of the deferred path: 256-block totals of w = w_un / s and their prefix.
+// S1: fused-block (kPartPer) totals of w = w_un / s and their prefix.
 __global__ __launch_bounds__(kPartPer) void scan_bsum256_kernel(
     const double* __restrict__ w_un, const double* __restrict__ s_in, const double np_recip,
     const int64_t n, double* __restrict__ bsum, double* __restrict__ boff,
@@ -991,28 +813,8 @@ __global__ __launch_bounds__(kPartPer) void scan_bsum256_kernel(
 // ====================================================================
 // exact sequential cumsum (np.cumsum, particle_filter.py:212)
 // ====================================================================
-// S1: approximate totals of kNormPer-element blocks of w; the last block scans
-// them into boff (boff[nb] = total).  normalize_kernel produces the same
-// arrays as a by-product when the next step resamples.
-__global__ __launch_bounds__(kNormThreads) void scan_bsum_kernel(
-    const double* __restrict__ w, const int64_t n, double* __restrict__ bsum,
-    double* __restrict__ boff, unsigned* __restrict__ counter) {
-    __shared__ double sh[kNormThreads / 64 + 1];
-    const int64_t base = (int64_t)blockIdx.x * kNormPer + threadIdx.x;
-    double loc = 0.0;
-#pragma unroll
-    for (int k = 0; k < kNormEPT; ++k) {
-        const int64_t i = base + k * kNormThreads;
-        if (i < n) loc += w[i];
-    }
-    double tot;
-    block_excl_scan<double, kNormThreads>(loc, sh, tot);
-    if (threadIdx.x == 0) st_wt_d(&bsum[blockIdx.x], tot);
-    if (!arrive_last(counter)) return;
-    block_scan_array<double, kNormThreads>(bsum, boff, gridDim.x, boff + gridDim.x, sh);
-}
-
-// the weight an exact-cumsum pass reads: w itself, or w_un / s on the deferred path
+// the weight an exact-cumsum pass reads: w_un / s (s_div), or w itself where
+// the caller passes normalised weights (s_div null)
 __device__ __forceinline__ double scan_w(const double* __restrict__ w, const int64_t i,
                                          const double* __restrict__ s_div, const double np_recip) {
     return s_div ? norm_w(w[i], *s_div, np_recip) : w[i];
@@ -1156,77 +958,6 @@ __device__ void serial_fold(const SpecialIn* __restrict__ spec, SpecialOut* __re
         }
     } else if (threadIdx.x == 0) {
         flags[kFlagFallback] = 0;
-    }
-}
-
-// S5: scatter the special elements into an ordered list (write-through); the
-// last block folds them (single GPU).  Multi-GPU gathers the lists first and
-// runs scan_fold_kernel on the concatenation.
-__global__ __launch_bounds__(kScanThreads) void scan_emit_kernel(
-    const double* __restrict__ w, const int64_t n, const double* __restrict__ approx,
-    const uint64_t* __restrict__ kincl, const int32_t* __restrict__ fexcl,
-    const uint64_t* __restrict__ boffk, const int32_t* __restrict__ bofff,
-    SpecialIn* __restrict__ spec, const int64_t gbase, SpecialOut* __restrict__ spec_out,
-    const int32_t* __restrict__ nspec_p, const uint64_t* __restrict__ ktot_p,
-    const int32_t do_fold, double* __restrict__ c, unsigned* __restrict__ counter,
-    int32_t* __restrict__ flags, const int32_t force, const double* __restrict__ s_div,
-    const double np_recip) {
-    if (!force && flags[kFlagResample] != 1) return;
-    const int64_t base = (int64_t)blockIdx.x * kScanBlock + threadIdx.x * kScanPer;
-    for (int k = 0; k < kScanPer; ++k) {
-        const int64_t i = base + k;
-        if (i >= n) break;
-        const int32_t f = fexcl[i];
-        if (f & 1) {
-            const int32_t m = bofff[blockIdx.x] + (f >> 1);
-            SpecialIn s;
-            s.idx = gbase + i;
-            s.P = boffk[blockIdx.x] + kincl[i];
-            s.w = scan_w(w, i, s_div, np_recip);
-            s.E = sum_binade(approx[i]);
-            s.pad = 0;
-            st_wt_struct(&spec[m], s);
-        }
-    }
-    if (!do_fold) return;
-    if (!arrive_last(counter)) return;
-    serial_fold(spec, spec_out, *nspec_p, *ktot_p, n, flags, w, c, n, true, s_div, np_recip);
-}
-
-// S6 stand-alone (multi-GPU: over the gathered global list)
-__global__ __launch_bounds__(256) void scan_fold_kernel(
-    const SpecialIn* __restrict__ spec, SpecialOut* __restrict__ out, const int32_t* __restrict__ M,
-    const uint64_t* __restrict__ ktot, const int64_t n_total, int32_t* __restrict__ flags,
-    const double* __restrict__ w, double* __restrict__ c, const int64_t n_local) {
-    serial_fold(spec, out, *M, *ktot, n_total, flags, w, c, n_local, false, nullptr, 0.0);
-}
-
-// S7: expand the exact cumsum from the specials.  spec_base / k_base: global
-// special count and increment prefix before local element 0 (multi-GPU).
-__global__ __launch_bounds__(kScanThreads) void scan_expand_kernel(
-    const int64_t n, const uint64_t* __restrict__ kincl, const int32_t* __restrict__ fexcl,
-    const uint64_t* __restrict__ boffk, const int32_t* __restrict__ bofff,
-    const SpecialOut* __restrict__ so, double* __restrict__ c, const int32_t* __restrict__ flags,
-    const int32_t* __restrict__ spec_base, const uint64_t* __restrict__ k_base,
-    const int32_t force) {
-    if (!force && flags[kFlagResample] != 1) return;
-    if (flags[kFlagFallback]) return;
-    const int64_t base = (int64_t)blockIdx.x * kScanBlock + threadIdx.x * kScanPer;
-    const uint64_t bko = boffk[blockIdx.x] + (k_base ? *k_base : 0);
-    const int32_t bfo = bofff[blockIdx.x] + (spec_base ? *spec_base : 0);
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) {
-        const int64_t i = base + k;
-        if (i >= n) break;
-        const int32_t f = fexcl[i];
-        const int32_t m = bfo + (f >> 1);
-        if (f & 1) {
-            c[i] = so[m].cs;
-        } else {
-            const SpecialOut& p = so[m - 1];
-            const uint64_t K = bko + kincl[i] - p.P;
-            c[i] = p.cs + (double)K * ldexp(1.0, p.E - 52);
-        }
     }
 }
 

@@ -343,7 +343,7 @@ def test_step_end_against_numpy_on_the_devices_weights(slamhip_pf, n):
     1e-12, the covariance to 1e-8 against np.cov of the device's state.  One
     size per finalize form: 2^20 the one-workgroup fast kernel, 2^21 + 12,345
     the fast kernel after the slice pre-pass, 2^24 + 12,345 (17 slices, 2,049
-    buffers) the general finalize_deferred_kernel."""
+    buffers) the general kernel, finalize_general_kernel."""
     import bench
     lm, zs, (vel, omega, dt) = bench.simulate_world(8)
     ctl = np.tile([vel, omega], (8, 1))

@@ -40,7 +40,8 @@ step end adds the finalize's slice pre-pass (pf_finalize.inl), 2^21 + 12,345
 and 2^23 particles with 20 landmarks (the oracle's per-particle factors at
 2^23 x 100 would need ~13 GB of host memory per step) and ESS_TH = NP / 10 (a
 constructor parameter; with 20 landmarks NP / 100 is first crossed after ~8
-steps).
+steps); and 2^24 + 12,345 particles (17 slices), the smallest size whose step
+end is the general kernel, for two steps with the second one resampling.
 """
 import os
 
@@ -217,3 +218,18 @@ def test_2p23_single_handle_lockstep_vs_oracle():
     n = 1 << 23
     run_lockstep(n, 20, 8, seed=11, lm_seed=25, obs_seed=26, min_resamples=2, batches=(3, 4, 1),
                  ess_th=n / 10)
+
+
+def test_general_step_end_hands_off_to_a_resampling_step():
+    """2^24 + 12,345 particles: 17 finalize slices, the smallest size the step
+    end's dispatch sends to finalize_general_kernel.  Step 0's end writes the
+    block-total prefix (fin_next_prefix's generic branch) that step 1's exact
+    cumsum and gather read: in handle B both steps run inside one two-step
+    graph batch, so nothing recomputes the prefix in between, and its records
+    and final state must equal the lockstep handle's bit for bit.  With 4
+    landmarks the oracle's ESS after step 0 is about 0.63 NP, so ESS_TH =
+    0.8 NP makes step 1 resample."""
+    n = (1 << 24) + 12345
+    inside = run_lockstep(n, 4, 2, seed=13, lm_seed=27, obs_seed=28, min_resamples=1, batches=(2,),
+                          ess_th=0.8 * n)
+    assert inside == 1

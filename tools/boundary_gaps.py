@@ -21,7 +21,7 @@ import numpy as np
 ap = argparse.ArgumentParser()
 ap.add_argument("trace")
 ap.add_argument("--split", type=float, default=3.0)
-ap.add_argument("--fused", default="pf_fused_kernel<1, 1, false, true")
+ap.add_argument("--fused", default="pf_fused_kernel<1, 1, false")   # <motion, lik, host noise, WT>: either store form
 args = ap.parse_args()
 
 rows = []

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Static instruction histogram of one kernel in a hipcc -S dump (device ISA).
 
-    python tools/isa_hist.py /tmp/isa/pf_api.s 'pf_fused_kernelILi1ELi1ELb0ELb1E'
+    python tools/isa_hist.py /tmp/isa/pf_api.s 'pf_fused_kernelILi1ELi1ELb0ELb1EE'
+
+(the bench's instantiation: <velocity, log-sum, device noise, write-through>).
 
 Prints the kernel's register/scratch metadata and its instruction mix by class
 (static counts: loop bodies count once; use the PMC SQ_INSTS_* for dynamic).

@@ -84,11 +84,11 @@ def main(src, tag):
         return rec
 
     # the bench's kernel (velocity, log-sum; the 2^20 handle's write-through instantiation)
-    key = "pf_fused_kernel<1, 1, false, true, true>"
+    key = "pf_fused_kernel<1, 1, false, true>"
     if key in out and "hbm_read_bytes" in out[key] and "hbm_write_bytes" in out[key]:
         main_rec = summary(key)
         kernels = {}
-        pkey = "pf_fused_kernel<1, 0, false, true, true>"  # the reference-literal product mode
+        pkey = "pf_fused_kernel<1, 0, false, true>"  # the reference-literal product mode
         if pkey in out:
             kernels["product"] = summary(pkey)
         sys.path.insert(0, os.getcwd())

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-variant fused-kernel counters from tools/pmc_variants.sh output
 (development tool): VALU / SALU / LDS instructions per wave and the wait
-fractions of pf_fused_kernel<1, 1, false, true> at the bench's grid."""
+fractions of pf_fused_kernel<1, 1, false, true> (velocity, log-sum, device
+noise, write-through stores) at the bench's grid."""
 import collections
 import csv
 import glob
