@@ -126,6 +126,11 @@ int slam_pf_weight_sum(slam_pf* h, double* sum_out);
  * / Philox-2x32-10 + Box-Muller; not a reference interface), out: count x 6. */
 int slam_debug_pair_normals(int device, uint64_t p0, int64_t count, uint32_t rstep, uint64_t seed,
                             double* out);
+/* Diagnostics: what this library holds in this process right now, over all
+ * handles and the stateless entry points' scratch: out[0] device bytes, out[1]
+ * pinned host bytes, out[2] events.  Exact counts kept by the library's one
+ * allocator (not a free-memory query, which other users of the card move). */
+int slam_debug_live_resources(int64_t out[3]);
 
 /* Device-resident multi-step run (bench path): observations for n_steps steps
  * are uploaded once; steps are enqueued back to back with no host sync.  A

@@ -1,5 +1,5 @@
-// api_common.hip -- version, thread-local error text, device query.
-#include "common.hpp"
+// api_common.hip -- version, thread-local error text, device query, live resources.
+#include "device_mem.hpp"
 
 namespace slam {
 
@@ -26,6 +26,14 @@ int slam_device_count(int* n) {
     hipError_t e = hipGetDeviceCount(&c);
     if (e != hipSuccess) c = 0;
     *n = c;
+    return SLAM_OK;
+}
+
+int slam_debug_live_resources(int64_t out[3]) {
+    SLAM_ARG_CHECK(out != nullptr, "slam_debug_live_resources: out is NULL");
+    out[0] = slam::g_live.device_bytes;
+    out[1] = slam::g_live.pinned_bytes;
+    out[2] = slam::g_live.events;
     return SLAM_OK;
 }
 

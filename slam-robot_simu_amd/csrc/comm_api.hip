@@ -15,7 +15,7 @@
 #include <rccl/rccl.h>
 
 #include "comm.hpp"
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace slam {
 
@@ -149,13 +149,14 @@ int slam_comm_create(const uint8_t* id, int32_t world, int32_t rank, int device,
     ncclComm_t nc = nullptr;
     const ncclResult_t r = api->comm_init_rank(&nc, world, uid, rank);
     if (r != ncclSuccess) return rccl_fail(api, r, "ncclCommInitRank");
-    slam_comm* h = new slam_comm();
+    HandlePtr<slam_comm, slam_comm_destroy> hp(new slam_comm());
+    slam_comm* h = hp.get();
     h->c.world = world;
     h->c.rank = rank;
     h->c.device = device;
     h->c.nccl = nc;
     h->c.api = api;
-    *out = h;
+    *out = hp.release();
     return SLAM_OK;
 }
 
@@ -181,15 +182,14 @@ int slam_comm_info(slam_comm* h, int32_t* world, int32_t* rank) {
 int slam_comm_all_gather_host(slam_comm* h, const void* send, void* recv, int64_t bytes) {
     SLAM_ARG_CHECK(h && send && recv && bytes > 0, "slam_comm_all_gather_host: bad argument");
     SLAM_HIP_TRY(hipSetDevice(h->c.device));
-    void* d = nullptr;
-    SLAM_HIP_TRY(hipMalloc(&d, (size_t)bytes * (h->c.world + 1)));
-    char* dsend = (char*)d + (size_t)bytes * h->c.world;
+    DeviceMem mem;
+    char* d = nullptr;
+    int rc = mem.alloc(&d, (size_t)bytes * (h->c.world + 1));
+    if (rc) return rc;
+    char* dsend = d + (size_t)bytes * h->c.world;
     hipStream_t s = nullptr;
-    int rc = SLAM_OK;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipFree(d);
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess)
         return fail(SLAM_ERR_HIP, "slam_comm_all_gather_host: stream creation failed");
-    }
     if (hipMemcpyAsync(dsend, send, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
         rc = fail(SLAM_ERR_HIP, "slam_comm_all_gather_host: upload failed");
     if (!rc) rc = comm_all_gather(h->c, dsend, d, (size_t)bytes, s);
@@ -198,7 +198,6 @@ int slam_comm_all_gather_host(slam_comm* h, const void* send, void* recv, int64_
     if (!rc && hipStreamSynchronize(s) != hipSuccess)
         rc = fail(SLAM_ERR_HIP, "slam_comm_all_gather_host: synchronize failed");
     (void)hipStreamDestroy(s);
-    (void)hipFree(d);
     return rc;
 }
 

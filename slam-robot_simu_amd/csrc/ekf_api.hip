@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "ekf_kernels.inl"
 
 using namespace slam;
@@ -19,6 +20,7 @@ struct slam_ekf {
     int device = 0;
     int64_t batch = 0;
     hipStream_t stream = nullptr;
+    DeviceMem mem;
     double* xs = nullptr;          // [3][B]
     double* Ps = nullptr;          // [9][B]
     double* z = nullptr;           // staging [steps][B][2]
@@ -38,6 +40,7 @@ struct slam_ekfslam {
     int32_t frag_pf = 0;           // experiment: where the next P block is requested
     int32_t apply_lds = 0;         // SLAM_EKS_APPLY=lds: the one-wave-per-row K = PH^T S^-1
     hipStream_t stream = nullptr;
+    DeviceMem mem;
     double* P = nullptr;           // n x ld, lower triangle current
     double* mu = nullptr;          // n
     double* pht = nullptr;         // n_pad x M
@@ -73,11 +76,13 @@ EKFConst ekf_const(const slam_ekf_config& c) {
 
 int ekf_reserve(slam_ekf* h, int32_t steps) {
     if (steps <= h->cap_steps) return SLAM_OK;
-    if (h->z) SLAM_HIP_TRY(hipFree(h->z));
-    if (h->xh) SLAM_HIP_TRY(hipFree(h->xh));
-    h->z = h->xh = nullptr;
-    SLAM_HIP_TRY(hipMalloc(&h->z, (size_t)steps * h->batch * 2 * sizeof(double)));
-    SLAM_HIP_TRY(hipMalloc(&h->xh, (size_t)steps * h->batch * 3 * sizeof(double)));
+    h->mem.release(h->z);
+    h->mem.release(h->xh);
+    h->cap_steps = 0;
+    int rc;
+    if ((rc = h->mem.alloc(&h->z, (size_t)steps * h->batch * 2)) ||
+        (rc = h->mem.alloc(&h->xh, (size_t)steps * h->batch * 3)))
+        return rc;
     h->cap_steps = steps;
     return SLAM_OK;
 }
@@ -254,35 +259,31 @@ int slam_ekf_create(const slam_ekf_config* cfg, int64_t batch, int device, slam_
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return fail(SLAM_ERR_ARG, "slam_ekf_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_ekf* h = new slam_ekf();
+    HandlePtr<slam_ekf, slam_ekf_destroy> hp(new slam_ekf());
+    slam_ekf* h = hp.get();
     h->cfg = *cfg;
     h->device = device;
     h->batch = batch;
-    auto bail = [&](int rc) {
-        slam_ekf_destroy(h);
-        return rc;
-    };
+    DeviceMem& m = h->mem;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->xs, 3 * batch * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->Ps, 9 * batch * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->xm, 3 * batch * sizeof(double)) != hipSuccess)
-        return bail(fail(SLAM_ERR_HIP, "slam_ekf_create: allocation failed"));
+        m.alloc(&h->xs, 3 * (size_t)batch) || m.alloc(&h->Ps, 9 * (size_t)batch) ||
+        m.alloc(&h->xm, 3 * (size_t)batch))
+        return fail(SLAM_ERR_HIP, "slam_ekf_create: allocation failed");
     std::vector<double> x0((size_t)batch * 3), p0((size_t)batch * 9);
     for (int64_t b = 0; b < batch; ++b) {
         std::memcpy(&x0[b * 3], cfg->x0, 3 * sizeof(double));
         std::memcpy(&p0[b * 9], cfg->p0, 9 * sizeof(double));
     }
     int rc = slam_ekf_set_state(h, x0.data(), p0.data());
-    if (rc != SLAM_OK) return bail(rc);
-    *out = h;
+    if (rc != SLAM_OK) return rc;
+    *out = hp.release();
     return SLAM_OK;
 }
 
 int slam_ekf_destroy(slam_ekf* h) {
     if (!h) return SLAM_OK;
     (void)hipSetDevice(h->device);
-    for (double* p : {h->xs, h->Ps, h->z, h->xh, h->xm})
-        if (p) (void)hipFree(p);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SLAM_OK;
@@ -401,7 +402,8 @@ int slam_ekfslam_create(const slam_ekfslam_config* cfg, int64_t n_landmarks, int
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return fail(SLAM_ERR_ARG, "slam_ekfslam_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_ekfslam* h = new slam_ekfslam();
+    HandlePtr<slam_ekfslam, slam_ekfslam_destroy> hp(new slam_ekfslam());
+    slam_ekfslam* h = hp.get();
     h->cfg = *cfg;
     h->device = device;
     h->n_lm = n_landmarks;
@@ -415,10 +417,6 @@ int slam_ekfslam_create(const slam_ekfslam_config* cfg, int64_t n_landmarks, int
 #endif
     h->ld = (h->n + SLAM_EKS_LD_ALIGN - 1) / SLAM_EKS_LD_ALIGN * SLAM_EKS_LD_ALIGN + SLAM_EKS_LD_SKEW;
     h->n_pad = (h->n + kEksTile - 1) / kEksTile * kEksTile;
-    auto bail = [&](int rc) {
-        slam_ekfslam_destroy(h);
-        return rc;
-    };
     {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, eks_rank_update_pipelined_kernel,
@@ -445,46 +443,35 @@ int slam_ekfslam_create(const slam_ekfslam_config* cfg, int64_t n_landmarks, int
     }
     const size_t pbytes = (size_t)h->n * h->ld * sizeof(double);
     const size_t rows = (size_t)h->n_pad * kEksMaxM;
+    DeviceMem& m = h->mem;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->P, pbytes) != hipSuccess ||
-        hipMalloc(&h->mu, h->n * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->pht, rows * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->kg, rows * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->kf, (size_t)h->n_pad * kEksPipeK * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->hf, (size_t)h->n_pad * kEksPipeK * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->hs, (kEksMaxM / 3) * 18 * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->e, kEksMaxM * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->rd, kEksMaxM * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->sinv, kEksMaxM * kEksMaxM * sizeof(double)) != hipSuccess ||
-        hipMalloc(&h->ids, (kEksMaxM / 3) * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&h->diag, h->n * sizeof(double)) != hipSuccess)
-        return bail(fail(SLAM_ERR_HIP, "slam_ekfslam_create: allocation failed (P is n^2 fp64)"));
+        m.alloc(&h->P, (size_t)h->n * h->ld) || m.alloc(&h->mu, (size_t)h->n) ||
+        m.alloc(&h->pht, rows) || m.alloc(&h->kg, rows) ||
+        m.alloc(&h->kf, (size_t)h->n_pad * kEksPipeK) || m.alloc(&h->hf, (size_t)h->n_pad * kEksPipeK) ||
+        m.alloc(&h->hs, (kEksMaxM / 3) * 18) || m.alloc(&h->e, kEksMaxM) || m.alloc(&h->rd, kEksMaxM) ||
+        m.alloc(&h->sinv, kEksMaxM * kEksMaxM) || m.alloc(&h->ids, kEksMaxM / 3) ||
+        m.alloc(&h->diag, (size_t)h->n))
+        return fail(SLAM_ERR_HIP, "slam_ekfslam_create: allocation failed (P is n^2 fp64)");
     for (auto& e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess)
-            return bail(fail(SLAM_ERR_HIP, "slam_ekfslam_create: event creation failed"));
+        if (m.event(&e)) return fail(SLAM_ERR_HIP, "slam_ekfslam_create: event creation failed");
     if (hipMemsetAsync(h->P, 0, pbytes, h->stream) != hipSuccess ||
         hipMemsetAsync(h->mu, 0, h->n * sizeof(double), h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess)
-        return bail(fail(SLAM_ERR_HIP, "slam_ekfslam_create: initialisation failed"));
+        return fail(SLAM_ERR_HIP, "slam_ekfslam_create: initialisation failed");
     const size_t big = (size_t)kEksMaxM * kEksMaxM * sizeof(double);
     if (hipFuncSetAttribute((const void*)eks_gain_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)big) != hipSuccess ||
         hipFuncSetAttribute((const void*)eks_apply_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)big) != hipSuccess)
-        return bail(fail(SLAM_ERR_HIP, "slam_ekfslam_create: LDS attribute failed"));
-    *out = h;
+        return fail(SLAM_ERR_HIP, "slam_ekfslam_create: LDS attribute failed");
+    *out = hp.release();
     return SLAM_OK;
 }
 
 int slam_ekfslam_destroy(slam_ekfslam* h) {
     if (!h) return SLAM_OK;
     (void)hipSetDevice(h->device);
-    for (void* p : {(void*)h->P, (void*)h->mu, (void*)h->pht, (void*)h->kg, (void*)h->kf, (void*)h->hf,
-                    (void*)h->hs,
-                    (void*)h->e, (void*)h->rd, (void*)h->sinv, (void*)h->ids, (void*)h->diag})
-        if (p) (void)hipFree(p);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SLAM_OK;

@@ -14,9 +14,7 @@
 // the ellipse angle is the device atan2 (within an ulp of the C library's).
 // Matrices whose norm needs dsyevd's / dsteqr's scaling (max |entry| outside
 // ~[1e-122, 1e153]) are flagged (NaN outputs), not approximated.
-#include <mutex>
-
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace slam {
 
@@ -148,18 +146,6 @@ __global__ __launch_bounds__(256) void error_ellipse_kernel(const int64_t n,
     out[3 * k + 2] = ang;
 }
 
-namespace {
-struct EllipseScratch {
-    std::mutex mu;
-    size_t cap = 0;
-    double* buf = nullptr;
-    hipStream_t stream = nullptr;
-};
-EllipseScratch& ellipse_scratch(int device) {
-    static EllipseScratch s[64];
-    return s[device & 63];
-}
-}  // namespace
 }  // namespace slam
 
 using namespace slam;
@@ -171,19 +157,12 @@ extern "C" int slam_error_ellipse(int64_t n, const double* covs, double chi, int
     int ndev = 0;
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev && device < 64, "slam_error_ellipse: no such HIP device");
-    EllipseScratch& sc = ellipse_scratch(device);
+    StaticScratch& sc = static_scratch<struct EllipseTag>(device);      // cap in covariances
     std::lock_guard<std::mutex> lock(sc.mu);
-    SLAM_HIP_TRY(hipSetDevice(device));
-    if (!sc.stream) SLAM_HIP_TRY(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
-    if ((size_t)n > sc.cap) {
-        if (sc.buf) (void)hipFree(sc.buf);
-        sc.buf = nullptr;
-        sc.cap = 0;
-        SLAM_HIP_TRY(hipMalloc(&sc.buf, sizeof(double) * 7 * (size_t)n));
-        sc.cap = (size_t)n;
-    }
-    double* d_cov = sc.buf;
-    double* d_out = sc.buf + 4 * sc.cap;
+    const int rc = sc.begin(device, (size_t)n, sizeof(double) * 7);
+    if (rc) return rc;
+    double* d_cov = (double*)sc.buf;
+    double* d_out = d_cov + 4 * sc.cap;
     SLAM_HIP_TRY(hipMemcpyAsync(d_cov, covs, 32 * n, hipMemcpyHostToDevice, sc.stream));
     error_ellipse_kernel<<<(unsigned)((n + 255) / 256), 256, 0, sc.stream>>>(n, d_cov, chi,
                                                                             column_vectors ? 1 : 0, d_out);

@@ -8,7 +8,8 @@
 
 struct slam_fs {
     slam_fs_config cfg;
-    slam_pf* pf = nullptr;
+    slam_pf* pf = nullptr;                 // the inner filter: destroyed with this handle
+    DeviceMem mem;                         // everything else below
     int64_t n = 0, npad = 0;
     int32_t nl = 0;
     double* map[2] = {nullptr, nullptr};   // ping-pong halves, [NL][5][npad]
@@ -101,37 +102,26 @@ FsObs fs_make_obs(const slam_fs* f, int64_t id, const double* o) {
     return r;
 }
 
+// grow-only buffer of the handle: release, allocate, then the capacity
+template <typename T>
+int fs_reserve(slam_fs* f, T*& p, int64_t& cap, int64_t want, size_t count) {
+    if (want <= cap) return SLAM_OK;
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    f->mem.release(p);
+    cap = 0;
+    const int rc = f->mem.alloc(&p, count);
+    if (rc) return rc;
+    cap = want;
+    return SLAM_OK;
+}
 int fs_reserve_obs(slam_fs* f, int64_t count) {
-    if (count <= f->obs_cap) return SLAM_OK;
-    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
-    if (f->obs_dev) (void)hipFree(f->obs_dev);
-    f->obs_dev = nullptr;
-    f->obs_cap = 0;
-    SLAM_HIP_TRY(hipMalloc((void**)&f->obs_dev, sizeof(FsObs) * (size_t)count));
-    f->obs_cap = count;
-    return SLAM_OK;
+    return fs_reserve(f, f->obs_dev, f->obs_cap, count, (size_t)count);
 }
-
 int fs_reserve_assoc(slam_fs* f, int64_t k) {
-    if (k <= f->assoc_cap) return SLAM_OK;
-    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
-    if (f->assoc_dev) (void)hipFree(f->assoc_dev);
-    f->assoc_dev = nullptr;
-    f->assoc_cap = 0;
-    SLAM_HIP_TRY(hipMalloc((void**)&f->assoc_dev, sizeof(int32_t) * (size_t)k * (size_t)f->npad));
-    f->assoc_cap = k;
-    return SLAM_OK;
+    return fs_reserve(f, f->assoc_dev, f->assoc_cap, k, (size_t)k * (size_t)f->npad);
 }
-
 int fs_reserve_stage(slam_fs* f, int64_t doubles) {
-    if (doubles <= f->stage_cap) return SLAM_OK;
-    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
-    if (f->stage) (void)hipFree(f->stage);
-    f->stage = nullptr;
-    f->stage_cap = 0;
-    SLAM_HIP_TRY(hipMalloc((void**)&f->stage, sizeof(double) * (size_t)doubles));
-    f->stage_cap = doubles;
-    return SLAM_OK;
+    return fs_reserve(f, f->stage, f->stage_cap, doubles, (size_t)doubles);
 }
 
 void fs_tic(slam_fs* f, int k) {
@@ -366,6 +356,44 @@ int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* 
 
 namespace {
 
+// the device side of fs_create_impl
+int fs_create_buffers(slam_fs* f, const slam_fs_assoc_config* acfg) {
+    DeviceMem& m = f->mem;
+    const hipStream_t st = f->pf->stream;
+    const size_t nl = (size_t)f->nl, npad = (size_t)f->npad;
+    const size_t map_count = (size_t)kFsComp * nl * npad;
+    int rc;
+    for (int k = 0; k < 2; ++k) {
+        if ((rc = m.alloc(&f->map[k], map_count))) return rc;
+        SLAM_HIP_TRY(hipMemsetAsync(f->map[k], 0, sizeof(double) * map_count, st));
+    }
+    if ((rc = m.alloc(&f->L, npad)) || (rc = m.alloc(&f->bmax, (size_t)f->nb + 1)) ||
+        (rc = m.alloc(&f->seen_dev, nl)) || (rc = m.alloc(&f->list_dev, nl)))
+        return rc;
+    SLAM_HIP_TRY(hipMemsetAsync(f->seen_dev, 0, sizeof(int32_t) * nl, st));
+    if (acfg) {
+        f->assoc = true;
+        f->acfg = *acfg;
+        f->acfg.record = acfg->record ? 1 : 0;
+        for (int k = 0; k < 2; ++k) {
+            if ((rc = m.alloc(&f->cnt[k], npad))) return rc;
+            SLAM_HIP_TRY(hipMemsetAsync(f->cnt[k], 0, sizeof(int32_t) * npad, st));
+        }
+        if ((rc = m.alloc(&f->stamp, npad * nl))) return rc;
+        SLAM_HIP_TRY(hipMemsetAsync(f->stamp, 0, sizeof(int32_t) * npad * nl, st));
+        if ((rc = m.alloc(&f->bcnt, (size_t)f->nb)) ||
+            (rc = m.alloc_pinned(&f->cmax_pin, &f->cmax_pin_dev, 1,
+                                 hipHostMallocMapped | hipHostMallocCoherent)))
+            return rc;
+        *f->cmax_pin = 0;
+    }
+    for (auto& pr : f->ev)
+        for (auto& ev : pr)
+            if ((rc = m.event(&ev))) return rc;
+    SLAM_HIP_TRY(hipStreamSynchronize(st));
+    return SLAM_OK;
+}
+
 // slam_fs_create, and slam_fs_create_assoc's second half (acfg != NULL)
 int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, int64_t n_particles,
                    int32_t n_landmarks, int device, slam_fs** out) {
@@ -385,56 +413,19 @@ int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, 
     slam_pf* pf = nullptr;
     int rc = create_impl(&pc, n_particles, n_particles, 0, 0, nullptr, device, &pf, false);
     if (rc) return rc;
-    slam_fs* f = new slam_fs();
+    HandlePtr<slam_fs, slam_fs_destroy> fp(new slam_fs());
+    slam_fs* f = fp.get();
+    f->pf = pf;
     f->cfg = *cfg;
     f->cfg.use_orient = cfg->use_orient ? 1 : 0;
-    f->pf = pf;
     f->n = n_particles;
     f->npad = (n_particles + kFsThreads - 1) / kFsThreads * kFsThreads;
     f->nl = n_landmarks;
     f->nb = (int32_t)(f->npad / kFsThreads);
     f->seen.assign((size_t)n_landmarks, 0);
-    const size_t map_bytes = sizeof(double) * (size_t)kFsComp * (size_t)n_landmarks * (size_t)f->npad;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc((void**)&f->map[k], map_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(f->map[k], 0, map_bytes, pf->stream);
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&f->L, sizeof(double) * (size_t)f->npad);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->bmax, sizeof(double) * ((size_t)f->nb + 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&f->seen_dev, sizeof(int32_t) * (size_t)n_landmarks);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->list_dev, sizeof(int32_t) * (size_t)n_landmarks);
-    if (e == hipSuccess)
-        e = hipMemsetAsync(f->seen_dev, 0, sizeof(int32_t) * (size_t)n_landmarks, pf->stream);
-    if (acfg) {
-        f->assoc = true;
-        f->acfg = *acfg;
-        f->acfg.record = acfg->record ? 1 : 0;
-        const size_t cb = sizeof(int32_t) * (size_t)f->npad;
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            e = hipMalloc((void**)&f->cnt[k], cb);
-            if (e == hipSuccess) e = hipMemsetAsync(f->cnt[k], 0, cb, pf->stream);
-        }
-        if (e == hipSuccess) e = hipMalloc((void**)&f->stamp, cb * (size_t)n_landmarks);
-        if (e == hipSuccess) e = hipMemsetAsync(f->stamp, 0, cb * (size_t)n_landmarks, pf->stream);
-        if (e == hipSuccess) e = hipMalloc((void**)&f->bcnt, sizeof(int32_t) * (size_t)f->nb);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void**)&f->cmax_pin, sizeof(int32_t),
-                              hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) {
-            *f->cmax_pin = 0;
-            e = hipHostGetDevicePointer((void**)&f->cmax_pin_dev, f->cmax_pin, 0);
-        }
-    }
-    for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        for (int q = 0; q < 2 && e == hipSuccess; ++q) e = hipEventCreate(&f->ev[k][q]);
-    if (e == hipSuccess) e = hipStreamSynchronize(pf->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        slam_fs_destroy(f);
-        return fail(SLAM_ERR_HIP, std::string("slam_fs_create: ") + hipGetErrorString(e));
-    }
-    *out = f;
+    if ((rc = fs_create_buffers(f, acfg)))
+        return fail(rc, std::string("slam_fs_create: ") + slam_last_error());
+    *out = fp.release();
     return SLAM_OK;
 }
 
@@ -457,23 +448,6 @@ int slam_fs_destroy(slam_fs* f) {
         (void)hipSetDevice(f->pf->device);
         (void)hipStreamSynchronize(f->pf->stream);
     }
-    for (int k = 0; k < 2; ++k)
-        if (f->map[k]) (void)hipFree(f->map[k]);
-    if (f->L) (void)hipFree(f->L);
-    if (f->bmax) (void)hipFree(f->bmax);
-    if (f->seen_dev) (void)hipFree(f->seen_dev);
-    if (f->list_dev) (void)hipFree(f->list_dev);
-    if (f->obs_dev) (void)hipFree(f->obs_dev);
-    if (f->stage) (void)hipFree(f->stage);
-    for (int k = 0; k < 2; ++k)
-        if (f->cnt[k]) (void)hipFree(f->cnt[k]);
-    if (f->stamp) (void)hipFree(f->stamp);
-    if (f->bcnt) (void)hipFree(f->bcnt);
-    if (f->assoc_dev) (void)hipFree(f->assoc_dev);
-    if (f->cmax_pin) (void)hipHostFree(f->cmax_pin);
-    for (auto& pr : f->ev)
-        for (auto& ev : pr)
-            if (ev) (void)hipEventDestroy(ev);
     slam_pf_destroy(f->pf);
     delete f;
     return SLAM_OK;

@@ -15,6 +15,7 @@
 #include <limits>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "graph_kernels.inl"
 #include "graph_build.inl"
 
@@ -26,8 +27,9 @@ struct slam_graph {
     slam_graph_config cfg;
     int device = 0;
     hipStream_t stream = nullptr;
-    std::vector<void*> allocs;     // dense-path buffers (per edge set, small systems only)
-    void* arena = nullptr;         // structure + solver buffers of the edge set (grow-only)
+    DeviceMem mem;
+    DeviceMem dense;               // dense-path buffers (per edge set, small systems only)
+    char* arena = nullptr;         // structure + solver buffers of the edge set (grow-only)
     size_t arena_bytes = 0;
     int64_t dense_n = 0;           // unknowns the dense buffers were sized for
     // poses
@@ -77,20 +79,6 @@ struct slam_graph {
 
 namespace {
 
-void free_list(std::vector<void*>& l) {
-    for (void* p : l) (void)hipFree(p);
-    l.clear();
-}
-
-template <typename T>
-int galloc(slam_graph* h, T** p, size_t count) {
-    void* q = nullptr;
-    SLAM_HIP_TRY(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return SLAM_OK;
-}
-
 #define GTRY(x)               \
     do {                      \
         int rc_ = (x);        \
@@ -133,7 +121,7 @@ int carve_edge_set(slam_graph* h, int64_t E, int64_t nt_ub, size_t tmp_bytes, Bu
     const int64_t K = 2 * E + nt_ub;
     const int64_t n = 3 * nt_ub;
     for (int pass = 0; pass < 2; ++pass) {
-        Carver c{pass ? (char*)h->arena : nullptr};
+        Carver c{pass ? h->arena : nullptr};
         h->edges = c.take<slam_graph_edge>(E);
         h->blocks = c.take<double>(42 * E);
         h->times = c.take<int64_t>(nt_ub);
@@ -188,10 +176,9 @@ int carve_edge_set(slam_graph* h, int64_t E, int64_t nt_ub, size_t tmp_bytes, Bu
             bs->tmp_bytes = tmp_bytes;
         }
         if (pass == 0 && c.off > h->arena_bytes) {
-            if (h->arena) SLAM_HIP_TRY(hipFree(h->arena));
-            h->arena = nullptr;
+            h->mem.release(h->arena);
             h->arena_bytes = 0;
-            SLAM_HIP_TRY(hipMalloc(&h->arena, c.off + c.off / 4));
+            GTRY(h->mem.alloc(&h->arena, c.off + c.off / 4));
             h->arena_bytes = c.off + c.off / 4;
         }
     }
@@ -202,13 +189,14 @@ int carve_edge_set(slam_graph* h, int64_t E, int64_t nt_ub, size_t tmp_bytes, Bu
 int dense_buffers(slam_graph* h, int64_t n) {
     if (n > kGraphDenseMax) return SLAM_OK;
     if (n <= h->dense_n && h->A) return SLAM_OK;
-    free_list(h->allocs);
-    GTRY(galloc(h, &h->A, n * n));
-    GTRY(galloc(h, &h->LU, n * n));
-    GTRY(galloc(h, &h->S, n * n));
-    GTRY(galloc(h, &h->V, n * (n + 1)));
-    GTRY(galloc(h, &h->lan, 3 * n + 8));
-    GTRY(galloc(h, &h->piv, n));
+    h->dense.clear();
+    h->dense_n = 0;
+    GTRY(h->dense.alloc(&h->A, n * n));
+    GTRY(h->dense.alloc(&h->LU, n * n));
+    GTRY(h->dense.alloc(&h->S, n * n));
+    GTRY(h->dense.alloc(&h->V, n * (n + 1)));
+    GTRY(h->dense.alloc(&h->lan, 3 * n + 8));
+    GTRY(h->dense.alloc(&h->piv, std::max<int64_t>(n, 1)));
     h->dense_n = n;
     return SLAM_OK;
 }
@@ -224,7 +212,7 @@ int finish_structure(slam_graph* h, int64_t E, int64_t nt, int64_t ns) {
     if (n <= kGraphDenseMax) {
         GTRY(dense_buffers(h, n));
     } else {
-        free_list(h->allocs);
+        h->dense.clear();
         h->A = h->LU = h->S = h->V = h->lan = nullptr;
         h->piv = nullptr;
         h->dense_n = 0;
@@ -302,10 +290,9 @@ int build_structure_device(slam_graph* h, int64_t E, const slam_graph_edge* ed) 
         // read back through pinned memory: the counts, then the distinct times
         const int64_t need = std::max<int64_t>(2, nt_ub);
         if (h->cnt_cap < need) {
-            if (h->cnt_host) SLAM_HIP_TRY(hipHostFree(h->cnt_host));
-            h->cnt_host = nullptr;
+            h->mem.release(h->cnt_host);
             h->cnt_cap = 0;
-            SLAM_HIP_TRY(hipHostMalloc(&h->cnt_host, (size_t)need * sizeof(int64_t)));
+            GTRY(h->mem.alloc_pinned(&h->cnt_host, nullptr, (size_t)need, hipHostMallocDefault));
             h->cnt_cap = need;
         }
         SLAM_HIP_TRY(hipMemcpyAsync(h->cnt_host, bs.cnt, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -884,7 +871,8 @@ int slam_graph_create(const slam_graph_config* cfg, int device, slam_graph** out
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return fail(SLAM_ERR_ARG, "slam_graph_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_graph* h = new slam_graph();
+    HandlePtr<slam_graph, slam_graph_destroy> hp(new slam_graph());
+    slam_graph* h = hp.get();
     h->cfg = *cfg;
     if (h->cfg.pcg_max_iter <= 0) h->cfg.pcg_max_iter = 10000;
     if (!(h->cfg.cond_tol > 0.0)) h->cfg.cond_tol = 1e-5;
@@ -892,46 +880,29 @@ int slam_graph_create(const slam_graph_config* cfg, int device, slam_graph** out
     if (!(h->cfg.pcg_tol > 0.0)) h->cfg.pcg_tol = 1e-10;
     h->device = device;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess) {
-        slam_graph_destroy(h);
+        hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess)
         return fail(SLAM_ERR_HIP, "slam_graph_create: stream creation failed");
-    }
+    DeviceMem& m = h->mem;
     for (auto& e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            slam_graph_destroy(h);
-            return fail(SLAM_ERR_HIP, "slam_graph_create: event creation failed");
-        }
+        if (m.event(&e)) return fail(SLAM_ERR_HIP, "slam_graph_create: event creation failed");
     for (auto& e : h->cev)
-        if (hipEventCreate(&e) != hipSuccess) {
-            slam_graph_destroy(h);
-            return fail(SLAM_ERR_HIP, "slam_graph_create: event creation failed");
-        }
-    if (hipHostMalloc(&h->pcg_host, sizeof(PcgState)) != hipSuccess ||
-        hipHostMalloc(&h->cond_host, sizeof(CondState)) != hipSuccess ||
-        hipHostMalloc(&h->cert_host, sizeof(CertState)) != hipSuccess) {
-        slam_graph_destroy(h);
+        if (m.event(&e)) return fail(SLAM_ERR_HIP, "slam_graph_create: event creation failed");
+    if (m.alloc_pinned(&h->pcg_host, nullptr, 1, hipHostMallocDefault) ||
+        m.alloc_pinned(&h->cond_host, nullptr, 1, hipHostMallocDefault) ||
+        m.alloc_pinned(&h->cert_host, nullptr, 1, hipHostMallocDefault))
         return fail(SLAM_ERR_HIP, "slam_graph_create: pinned state buffers");
-    }
-    *out = h;
+    *out = hp.release();
     return SLAM_OK;
 }
 
 int slam_graph_destroy(slam_graph* h) {
     if (!h) return SLAM_OK;
     (void)hipSetDevice(h->device);
-    free_list(h->allocs);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->poses) (void)hipFree(h->poses);
-    for (auto& e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->cev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->pcg_host) (void)hipHostFree(h->pcg_host);
-    if (h->cnt_host) (void)hipHostFree(h->cnt_host);
-    if (h->cond_host) (void)hipHostFree(h->cond_host);
-    if (h->cert_host) (void)hipHostFree(h->cert_host);
-    if (h->cstream) (void)hipStreamDestroy(h->cstream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    for (hipStream_t s : {h->cstream, h->stream})
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
     delete h;
     return SLAM_OK;
 }
@@ -940,9 +911,10 @@ int slam_graph_set_poses(slam_graph* h, int64_t n_poses, const double* poses) {
     SLAM_ARG_CHECK(h && poses && n_poses >= 1, "slam_graph_set_poses: bad arguments");
     SLAM_HIP_TRY(hipSetDevice(h->device));
     if (n_poses != h->T) {
-        if (h->poses) SLAM_HIP_TRY(hipFree(h->poses));
-        h->poses = nullptr;
-        SLAM_HIP_TRY(hipMalloc(&h->poses, 3 * n_poses * sizeof(double)));
+        h->mem.release(h->poses);
+        h->T = 0;
+        const int rc = h->mem.alloc(&h->poses, 3 * (size_t)n_poses);
+        if (rc) return rc;
         h->T = n_poses;
     }
     SLAM_HIP_TRY(hipMemcpyAsync(h->poses, poses, 3 * n_poses * sizeof(double),
@@ -1117,32 +1089,24 @@ int slam_graph_pair_halves(int64_t n_halves, const slam_graph_half* halves, int6
     int64_t *d_off = nullptr, *d_start = nullptr;
     slam_graph_half* d_half = nullptr;
     slam_graph_edge* d_edges = nullptr;
-    int rc = SLAM_OK;
-    if (hipMalloc(&d_off, pair_off.size() * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&d_start, lm_start.size() * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&d_half, grouped.size() * sizeof(slam_graph_half)) != hipSuccess ||
-        hipMalloc(&d_edges, (size_t)E * sizeof(slam_graph_edge)) != hipSuccess) {
-        rc = fail(SLAM_ERR_HIP, "slam_graph_pair_halves: device allocation failed");
-    } else if (hipMemcpy(d_off, pair_off.data(), pair_off.size() * sizeof(int64_t),
-                         hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(d_start, lm_start.data(), lm_start.size() * sizeof(int64_t),
-                         hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(d_half, grouped.data(), grouped.size() * sizeof(slam_graph_half),
-                         hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SLAM_ERR_HIP, "slam_graph_pair_halves: upload failed");
-    } else {
-        hipLaunchKernelGGL(graph_pair_kernel, dim3(nblk(E)), dim3(256), 0, nullptr, E,
-                           n_landmarks, d_off, d_start, d_half, d_edges);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(edges, d_edges, (size_t)E * sizeof(slam_graph_edge),
-                      hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(SLAM_ERR_HIP, "slam_graph_pair_halves: kernel or download failed");
-    }
-    (void)hipFree(d_off);
-    (void)hipFree(d_start);
-    (void)hipFree(d_half);
-    (void)hipFree(d_edges);
-    return rc;
+    DeviceMem mem;
+    if (mem.alloc(&d_off, pair_off.size()) || mem.alloc(&d_start, lm_start.size()) ||
+        mem.alloc(&d_half, grouped.size()) || mem.alloc(&d_edges, (size_t)E))
+        return fail(SLAM_ERR_HIP, "slam_graph_pair_halves: device allocation failed");
+    if (hipMemcpy(d_off, pair_off.data(), pair_off.size() * sizeof(int64_t), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(d_start, lm_start.data(), lm_start.size() * sizeof(int64_t), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(d_half, grouped.data(), grouped.size() * sizeof(slam_graph_half),
+                  hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SLAM_ERR_HIP, "slam_graph_pair_halves: upload failed");
+    hipLaunchKernelGGL(graph_pair_kernel, dim3(nblk(E)), dim3(256), 0, nullptr, E, n_landmarks, d_off,
+                       d_start, d_half, d_edges);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(edges, d_edges, (size_t)E * sizeof(slam_graph_edge), hipMemcpyDeviceToHost) !=
+            hipSuccess)
+        return fail(SLAM_ERR_HIP, "slam_graph_pair_halves: kernel or download failed");
+    return SLAM_OK;
 }
 
 int slam_graph_linearize_solve(const slam_graph_config* cfg, const slam_graph_edge* edges,

@@ -8,9 +8,7 @@
 // reference operation by operation (-ffp-contract=off): sin/cos of the two
 // headings are evaluated directly (not by angle addition as in the PF step
 // kernel), so the result is within the sin/cos ulp of NumPy's.
-#include <mutex>
-
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace slam {
 
@@ -63,23 +61,6 @@ __global__ __launch_bounds__(256) void motion_velocity_kernel(const int64_t n,
     out[3 * i + 2] = tn;
 }
 
-namespace {
-
-// grow-only device scratch per device for the one-shot entry point
-struct MotionScratch {
-    std::mutex mu;
-    int device = -1;
-    size_t cap = 0;      // poses
-    double* buf = nullptr;
-    hipStream_t stream = nullptr;
-};
-
-MotionScratch& scratch_for(int device) {
-    static MotionScratch s[64];
-    return s[device & 63];
-}
-
-}  // namespace
 }  // namespace slam
 
 using namespace slam;
@@ -91,21 +72,14 @@ extern "C" int slam_motion_velocity(const double* params, int64_t n, const doubl
     int ndev = 0;
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev && device < 64, "slam_motion_velocity: no such HIP device");
-    MotionScratch& sc = scratch_for(device);
+    StaticScratch& sc = static_scratch<struct MotionTag>(device);      // cap in poses
     std::lock_guard<std::mutex> lock(sc.mu);
-    SLAM_HIP_TRY(hipSetDevice(device));
-    if (!sc.stream) SLAM_HIP_TRY(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
     const size_t need = (size_t)n;
-    if (need > sc.cap) {
-        if (sc.buf) (void)hipFree(sc.buf);
-        sc.buf = nullptr;
-        sc.cap = 0;
-        SLAM_HIP_TRY(hipMalloc(&sc.buf, sizeof(double) * 9 * need));   // poses, noise, out
-        sc.cap = need;
-    }
-    double* d_pose = sc.buf;
-    double* d_noise = sc.buf + 3 * sc.cap;
-    double* d_out = sc.buf + 6 * sc.cap;
+    const int rc = sc.begin(device, need, sizeof(double) * 9);   // poses, noise, out
+    if (rc) return rc;
+    double* d_pose = (double*)sc.buf;
+    double* d_noise = d_pose + 3 * sc.cap;
+    double* d_out = d_pose + 6 * sc.cap;
     const size_t bytes = sizeof(double) * 3 * need;
     SLAM_HIP_TRY(hipMemcpyAsync(d_pose, poses, bytes, hipMemcpyHostToDevice, sc.stream));
     if (normals) SLAM_HIP_TRY(hipMemcpyAsync(d_noise, normals, bytes, hipMemcpyHostToDevice, sc.stream));

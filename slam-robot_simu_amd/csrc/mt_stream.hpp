@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_mem.hpp"
 #include "mt19937.hpp"
 
 namespace slam {
@@ -60,6 +61,9 @@ struct MtBuffers {
     int64_t need = 0;               // words a request may read past the position (+ margins)
     int32_t R = 1;                  // segments per round
     int64_t S = 0;                  // words per segment (a multiple of 624)
+    DeviceMem mem;                  // owns the buffers above
+
+    void reset() { *this = MtBuffers{}; }   // frees them
 };
 
 // glibc's log table from this process's libm, checked against log() (cached).
@@ -68,7 +72,6 @@ int glibc_log_table(GlibcLogTable* out);
 // Size the buffers for requests of up to g_cap normals after up to pre_cap
 // doubles (grow-only; a regrow keeps the stream state).
 int mt_reserve(MtBuffers& b, int64_t g_cap, int64_t pre_cap, int device);
-void mt_free(MtBuffers& b);
 
 int mt_set_state(MtBuffers& b, const uint32_t* key, int32_t pos, int32_t has_gauss, double gauss,
                  hipStream_t s);

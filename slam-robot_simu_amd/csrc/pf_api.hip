@@ -19,21 +19,6 @@
 
 namespace slam {
 
-// numpy pairwise split of a tail buffer (< 8192 elements): leaves + post-order program
-static void build_tail(int lo, int n, std::vector<int32_t>& leaves, std::vector<int32_t>& ops) {
-    if (n <= 128) {
-        ops.push_back((int32_t)(leaves.size() / 2));
-        leaves.push_back(lo);
-        leaves.push_back(n);
-        return;
-    }
-    int h = n / 2;
-    h -= h % 8;
-    build_tail(lo, h, leaves, ops);
-    build_tail(lo + h, n - h, leaves, ops);
-    ops.push_back(-1);
-}
-
 constexpr int kGraphLevels = 4;    // captured step graphs of 1, 2, 4 and 8 steps
 constexpr int kGraphSteps = 1 << (kGraphLevels - 1);
 constexpr int32_t kSetupCopyMax = 4096;   // batch controls the setup kernel copies itself
@@ -56,7 +41,7 @@ struct slam_pf {
     int32_t nl = 0;
     hipStream_t stream = nullptr;
     bool own_stream = true;
-    std::vector<void*> allocs;
+    DeviceMem mem;
     // state (ping-pong)
     double* x[2] = {nullptr, nullptr};
     double* y[2] = {nullptr, nullptr};
@@ -139,18 +124,6 @@ struct slam_pf {
 
 namespace {
 
-int halloc(slam_pf* h, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 8;
-    SLAM_HIP_TRY(hipMalloc(p, bytes));
-    h->allocs.push_back(*p);
-    return SLAM_OK;
-}
-
-template <typename T>
-int dalloc(slam_pf* h, T** p, size_t count) {
-    return halloc(h, (void**)p, count * sizeof(T));
-}
-
 int make_lik_const(slam_pf* h) { return lik_const_from(h->cfg.r_cov, h->nl, true, h->lc); }
 
 void make_predict_const(slam_pf* h) {
@@ -185,8 +158,8 @@ void tic(slam_pf* h, int k) {
     Timer& t = h->tm;
     if (t.used[k] == t.ev[k].size()) {
         hipEvent_t a, b;
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
+        (void)h->mem.event(&a);
+        (void)h->mem.event(&b);
         t.ev[k].push_back({a, b});
     }
     (void)hipEventRecord(t.ev[k][t.used[k]].first, h->stream);
@@ -238,41 +211,33 @@ int capture_steps(slam_pf* h, hipGraphExec_t& ge, int steps) {
     return SLAM_OK;
 }
 
-void release(slam_pf* h, void* p) {
-    if (!p) return;
-    (void)hipFree(p);
-    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), p), h->allocs.end());
-}
-
 // (Re)allocate the StepIO arrays for `steps` steps.
 int ensure_steps(slam_pf* h, int32_t steps) {
     if (steps <= h->cap) return SLAM_OK;
     drop_graphs(h);
-    release(h, h->ctl);
-    release(h, h->z_all);
-    release(h, h->zc);
-    release(h, h->ofs);
-    release(h, h->truth);
-    release(h, h->res_dev);
-    if (h->res_host) (void)hipHostFree(h->res_host);
-    h->res_host = nullptr;
-    if (h->ctl_pin) (void)hipHostFree(h->ctl_pin);
-    h->ctl_pin = nullptr;
+    DeviceMem& m = h->mem;
+    m.release(h->ctl);
+    m.release(h->z_all);
+    m.release(h->zc);
+    m.release(h->ofs);
+    m.release(h->truth);
+    m.release(h->res_dev);
+    m.release(h->res_host);
+    m.release(h->ctl_pin);
+    h->cap = 0;
     int rc;
     const size_t nlz = 2 * (size_t)std::max<int32_t>(h->nl, 1);
-    if ((rc = dalloc(h, &h->ctl, 2 * (size_t)steps)) || (rc = dalloc(h, &h->z_all, nlz * steps)) ||
-        (rc = dalloc(h, &h->zc, (size_t)kClosedWords * steps)) ||
-        (rc = dalloc(h, &h->ofs, (size_t)steps)) || (rc = dalloc(h, &h->truth, 4 * (size_t)steps)) ||
-        (rc = dalloc(h, &h->res_dev, (size_t)steps)))
+    if ((rc = m.alloc(&h->ctl, 2 * (size_t)steps)) || (rc = m.alloc(&h->z_all, nlz * steps)) ||
+        (rc = m.alloc(&h->zc, (size_t)kClosedWords * steps)) ||
+        (rc = m.alloc(&h->ofs, (size_t)steps)) || (rc = m.alloc(&h->truth, 4 * (size_t)steps)) ||
+        (rc = m.alloc(&h->res_dev, (size_t)steps)))
         return rc;
     // fine-grained host memory: the setup kernel reads the controls and the
     // export kernel stores the results over the host link, uncached
-    SLAM_HIP_TRY(hipHostMalloc((void**)&h->res_host, sizeof(slam_pf_result) * steps,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-    SLAM_HIP_TRY(hipHostMalloc((void**)&h->ctl_pin, 2 * sizeof(double) * steps,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-    SLAM_HIP_TRY(hipHostGetDevicePointer((void**)&h->res_host_dev, h->res_host, 0));
-    SLAM_HIP_TRY(hipHostGetDevicePointer((void**)&h->ctl_pin_dev, h->ctl_pin, 0));
+    const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
+    if ((rc = m.alloc_pinned(&h->res_host, &h->res_host_dev, (size_t)steps, pin)) ||
+        (rc = m.alloc_pinned(&h->ctl_pin, &h->ctl_pin_dev, 2 * (size_t)steps, pin)))
+        return rc;
     h->cap = steps;
     h->z_steps = 0;
     h->truth_steps = 0;
@@ -647,7 +612,8 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev, "slam_pf_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_pf* h = new slam_pf();
+    HandlePtr<slam_pf, slam_pf_destroy> hp(new slam_pf());
+    slam_pf* h = hp.get();
     h->cfg = *cfg;
     h->device = device;
     h->n = n_local;
@@ -655,10 +621,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     h->gbase = gbase;
     h->nl = n_landmarks;
     int rc = make_lik_const(h);
-    if (rc) {
-        delete h;
-        return rc;
-    }
+    if (rc) return rc;
     make_predict_const(h);
     const int64_t n = n_local;
     h->nb_scan = (int32_t)((n + kScanBlock - 1) / kScanBlock);
@@ -676,25 +639,19 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
         h->scan_merged = h->scan_merged_ok;
     }
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
+    if (e != hipSuccess)
         return fail(SLAM_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
-    }
-#define A(p, cnt)                                         \
-    if ((rc = dalloc(h, &(p), (size_t)(cnt))) != 0) {     \
-        slam_pf_destroy(h);                               \
-        return rc;                                        \
-    }
     // particle and weight arrays padded to whole fused blocks (the fused
     // kernel moves particle pairs with 16-byte loads and stores); a sharded
     // handle: npad staging slots on either side of each particle array for the
     // particles a resample receives from other ranks (DeferParts.goff)
+    auto A = [&](auto*& p, int64_t count) { return rc = h->mem.alloc(&p, (size_t)count); };
     const int64_t npad = (int64_t)h->nb_part * kPartPer;
     const int64_t side = dist_shard ? npad : 0;
     for (int k = 0; k < 2; ++k) {
-        A(h->x[k], npad + 2 * side);
-        A(h->y[k], npad + 2 * side);
-        A(h->th[k], npad + 2 * side);
+        if (A(h->x[k], npad + 2 * side)) return rc;
+        if (A(h->y[k], npad + 2 * side)) return rc;
+        if (A(h->th[k], npad + 2 * side)) return rc;
         if (npad > n || side) {
             SLAM_HIP_TRY(hipMemsetAsync(h->x[k], 0, sizeof(double) * (npad + 2 * side), h->stream));
             SLAM_HIP_TRY(hipMemsetAsync(h->y[k], 0, sizeof(double) * (npad + 2 * side), h->stream));
@@ -706,81 +663,78 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     }
     h->dp.goff = side;
     h->dp.glim = dist_shard ? 3 * npad : n;
-    A(h->w, n);
-    A(h->w_un, npad);
+    if (A(h->w, n)) return rc;
+    if (A(h->w_un, npad)) return rc;
     if (npad > n) SLAM_HIP_TRY(hipMemsetAsync(h->w_un, 0, sizeof(double) * npad, h->stream));
-    A(h->c, npad);
-    A(h->idx, n);
-    A(h->bsum, h->nb_part);
-    A(h->boff, h->nb_part + 1);
-    A(h->s_cur, 1);
-    A(h->dp.pmax, h->nb_part + 1);                        // + 1: the finalize's pair loads
-    A(h->dp.pidx, h->nb_part);
-    A(h->dp.ppre, h->nb_part);
-    for (int q = 0; q < 3; ++q) A(h->dp.pxe[q], h->nb_part);
-    for (int q = 0; q < 11; ++q) A(h->dp.ps[q], h->nb_part + 1);
-    A(h->dp.leaf, (size_t)(kPartPer / 128) * h->nb_part);
-    A(h->dp.mark, npad);
-    A(h->dp.carry, h->nb_part + 1);
+    if (A(h->c, npad)) return rc;
+    if (A(h->idx, n)) return rc;
+    if (A(h->bsum, h->nb_part)) return rc;
+    if (A(h->boff, h->nb_part + 1)) return rc;
+    if (A(h->s_cur, 1)) return rc;
+    if (A(h->dp.pmax, h->nb_part + 1)) return rc;   // + 1: the finalize's pair loads
+    if (A(h->dp.pidx, h->nb_part)) return rc;
+    if (A(h->dp.ppre, h->nb_part)) return rc;
+    for (int q = 0; q < 3; ++q) if (A(h->dp.pxe[q], h->nb_part)) return rc;
+    for (int q = 0; q < 11; ++q) if (A(h->dp.ps[q], h->nb_part + 1)) return rc;
+    if (A(h->dp.leaf, (size_t)(kPartPer / 128) * h->nb_part)) return rc;
+    if (A(h->dp.mark, npad)) return rc;
+    if (A(h->dp.carry, h->nb_part + 1)) return rc;
     if (h->nb_part > kFinThreads * kFinRegBlocks) {
         const int32_t per = kFinThreads * kFinRegBlocks;
         h->fsl.nsl = (h->nb_part + per - 1) / per;
-        A(h->fsl.m, h->fsl.nsl);
-        A(h->fsl.q, 11 * (size_t)h->fsl.nsl);
-        A(h->fsl.buf, std::max<int64_t>(n / kSumChunk, 1));
-        A(h->fsl.cblk, kSliceCand * (size_t)h->fsl.nsl);
-        A(h->fsl.cpm, kSliceCand * (size_t)h->fsl.nsl);
-        A(h->fsl.ncand, h->fsl.nsl);
-        A(h->fsl.pre, h->nb_part + 1);
-        A(h->fsl.u, h->fsl.nsl);
+        if (A(h->fsl.m, h->fsl.nsl)) return rc;
+        if (A(h->fsl.q, 11 * (size_t)h->fsl.nsl)) return rc;
+        if (A(h->fsl.buf, std::max<int64_t>(n / kSumChunk, 1))) return rc;
+        if (A(h->fsl.cblk, kSliceCand * (size_t)h->fsl.nsl)) return rc;
+        if (A(h->fsl.cpm, kSliceCand * (size_t)h->fsl.nsl)) return rc;
+        if (A(h->fsl.ncand, h->fsl.nsl)) return rc;
+        if (A(h->fsl.pre, h->nb_part + 1)) return rc;
+        if (A(h->fsl.u, h->fsl.nsl)) return rc;
     }
     SLAM_HIP_TRY(hipMemsetAsync(h->dp.mark, 0xff, sizeof(int64_t) * npad, h->stream));
     SLAM_HIP_TRY(hipMemsetAsync(h->dp.carry, 0, sizeof(int32_t) * (h->nb_part + 1), h->stream));
     // tile totals: 2048-element tiles (the sharded exchange) or 512-element wave tiles
     const int32_t ntile_max = std::max(h->nb_scan, h->nb_part);
-    A(h->bk, ntile_max);
-    A(h->boffk, ntile_max);
-    A(h->bf, ntile_max);
-    A(h->bofff, ntile_max);
-    A(h->ktot, 1);
-    A(h->nspec, 1);
+    if (A(h->bk, ntile_max)) return rc;
+    if (A(h->boffk, ntile_max)) return rc;
+    if (A(h->bf, ntile_max)) return rc;
+    if (A(h->bofff, ntile_max)) return rc;
+    if (A(h->ktot, 1)) return rc;
+    if (A(h->nspec, 1)) return rc;
     if (dist_shard) {
         // per-element scratch of the sharded exchange's exact cumsum (the
         // launches in pf_dist_api.inl; slam_dist_create takes dist shards only)
-        A(h->kincl, n);
-        A(h->fexcl, n);
-        A(h->spec_in, n);
+        if (A(h->kincl, n)) return rc;
+        if (A(h->fexcl, n)) return rc;
+        if (A(h->spec_in, n)) return rc;
     }
-    A(h->stage, n);
-    A(h->spec_out, n);
+    if (A(h->stage, n)) return rc;
+    if (A(h->spec_out, n)) return rc;
     if (h->scan_merged_ok) {
-        A(h->hand, (size_t)(h->nb_scan + kHandReplicas) * kHandGranules);
-        A(h->spec_tag, (size_t)n * kSpecGranules);
+        if (A(h->hand, (size_t)(h->nb_scan + kHandReplicas) * kHandGranules)) return rc;
+        if (A(h->spec_tag, (size_t)n * kSpecGranules)) return rc;
         SLAM_HIP_TRY(hipMemsetAsync(h->hand, 0, sizeof(uint64_t) * (h->nb_scan + kHandReplicas) * kHandGranules,
                                     h->stream));
         SLAM_HIP_TRY(hipMemsetAsync(h->spec_tag, 0, sizeof(uint64_t) * n * kSpecGranules, h->stream));
     }
-    A(h->part, h->nchunks);
-    A(h->wsum, 1);
+    if (A(h->part, h->nchunks)) return rc;
+    if (A(h->wsum, 1)) return rc;
     // [0..2] last estimate, [4..6] the one before, [7] moves of the first
     // expansion reference (closed_prep_reference)
-    A(h->refp, 8);
-    A(h->flags, kFlagWords);
-    A(h->tk, 4 * kTicketWords);
-    A(h->lm, 2 * std::max<int32_t>(n_landmarks, 1));
-    A(h->noise, 3 * n);
-    A(h->ctr, 4);
-#undef A
+    if (A(h->refp, 8)) return rc;
+    if (A(h->flags, kFlagWords)) return rc;
+    if (A(h->tk, 4 * kTicketWords)) return rc;
+    if (A(h->lm, 2 * std::max<int32_t>(n_landmarks, 1))) return rc;
+    if (A(h->noise, 3 * n)) return rc;
+    if (A(h->ctr, 4)) return rc;
     std::vector<int32_t> leaves, ops;
     const int tail = (int)(n % kSumChunk);
-    if (tail) build_tail(0, tail, leaves, ops);
+    if (tail) pairwise_sum_split(0, tail, leaves, ops);
     h->n_tail_leaves = (int32_t)(leaves.size() / 2);
     h->n_tail_ops = (int32_t)ops.size();
-    if ((rc = dalloc(h, &h->tail_leaves, leaves.size() + 2)) ||
-        (rc = dalloc(h, &h->tail_ops, ops.size() + 1)) || (rc = ensure_steps(h, 1))) {
-        slam_pf_destroy(h);
+    if ((rc = h->mem.alloc(&h->tail_leaves, leaves.size() + 2)) ||
+        (rc = h->mem.alloc(&h->tail_ops, ops.size() + 1)) || (rc = ensure_steps(h, 1)))
         return rc;
-    }
     if (tail) {
         SLAM_HIP_TRY(hipMemcpy(h->tail_leaves, leaves.data(), leaves.size() * 4, hipMemcpyHostToDevice));
         SLAM_HIP_TRY(hipMemcpy(h->tail_ops, ops.data(), ops.size() * 4, hipMemcpyHostToDevice));
@@ -808,7 +762,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     SLAM_HIP_TRY(hipMemsetD32((hipDeviceptr_t)(h->ctr + 2), -1, 2));   // no batch bounds yet
     if (n_landmarks > 0)
         SLAM_HIP_TRY(hipMemcpy(h->lm, landmarks, 2 * n_landmarks * sizeof(double), hipMemcpyHostToDevice));
-    *out = h;
+    *out = hp.release();
     return SLAM_OK;
 }
 
@@ -889,15 +843,6 @@ int slam_pf_destroy(slam_pf* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     drop_graphs(h);
-    mt_free(h->mtb);
-    for (void* p : h->allocs) (void)hipFree(p);
-    if (h->res_host) (void)hipHostFree(h->res_host);
-    if (h->ctl_pin) (void)hipHostFree(h->ctl_pin);
-    for (int k = 0; k < 4; ++k)
-        for (auto& pr : h->tm.ev[k]) {
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
     if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SLAM_OK;
@@ -1133,12 +1078,13 @@ int slam_debug_pair_normals(int device, uint64_t p0, int64_t count, uint32_t rst
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev, "slam_debug_pair_normals: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
+    DeviceMem mem;
     double* d = nullptr;
-    SLAM_HIP_TRY(hipMalloc(&d, 6 * count * sizeof(double)));
+    const int rc = mem.alloc(&d, 6 * (size_t)count);
+    if (rc) return rc;
     debug_pair_normals_kernel<<<grid_for(count, 256), 256>>>(p0, count, rstep, seed, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, d, 6 * count * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(SLAM_ERR_HIP, std::string("slam_debug_pair_normals: ") + hipGetErrorString(e));
     return SLAM_OK;
 }

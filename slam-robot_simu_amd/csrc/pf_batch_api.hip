@@ -9,6 +9,7 @@
 #include <limits>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "pf_batch.inl"
 
 using namespace slam;
@@ -19,7 +20,7 @@ struct slam_pfb {
     int32_t motion = 0, lik = 0;
     std::vector<slam_pf_config> cfgs;
     hipStream_t stream = nullptr;
-    std::vector<void*> allocs;
+    DeviceMem mem;
     double* x[2] = {nullptr, nullptr};
     double* y[2] = {nullptr, nullptr};
     double* th[2] = {nullptr, nullptr};
@@ -50,36 +51,6 @@ struct slam_pfb {
 
 namespace {
 
-// numpy pairwise split (n >= 8): leaves (lo, count) + post-order program
-void build_tree(int lo, int n, std::vector<int32_t>& leaves, std::vector<int32_t>& ops) {
-    if (n <= 128) {
-        ops.push_back((int32_t)(leaves.size() / 2));
-        leaves.push_back(lo);
-        leaves.push_back(n);
-        return;
-    }
-    int h = n / 2;
-    h -= h % 8;
-    build_tree(lo, h, leaves, ops);
-    build_tree(lo + h, n - h, leaves, ops);
-    ops.push_back(-1);
-}
-
-template <typename T>
-int dalloc(slam_pfb* h, T** p, size_t count) {
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = 8;
-    SLAM_HIP_TRY(hipMalloc((void**)p, bytes));
-    h->allocs.push_back(*p);
-    return SLAM_OK;
-}
-
-void release(slam_pfb* h, void* p) {
-    if (!p) return;
-    (void)hipFree(p);
-    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), p), h->allocs.end());
-}
-
 // [B][n] host rows <-> [B][npad] device rows
 int rows_to_device(slam_pfb* h, double* dst, const double* src) {
     SLAM_HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * h->npad, src, sizeof(double) * h->n,
@@ -94,12 +65,11 @@ int rows_to_host(slam_pfb* h, double* dst, const double* src) {
 
 int ensure_results(slam_pfb* h, size_t records) {
     if (records <= h->res_cap) return SLAM_OK;
-    if (h->res_host) (void)hipHostFree(h->res_host);
-    h->res_host = nullptr;
+    h->mem.release(h->res_host);
     h->res_cap = 0;
-    SLAM_HIP_TRY(hipHostMalloc((void**)&h->res_host, sizeof(slam_pf_result) * records,
-                               hipHostMallocMapped | hipHostMallocCoherent));
-    SLAM_HIP_TRY(hipHostGetDevicePointer((void**)&h->res_host_dev, h->res_host, 0));
+    const int rc = h->mem.alloc_pinned(&h->res_host, &h->res_host_dev, records,
+                                       hipHostMallocMapped | hipHostMallocCoherent);
+    if (rc) return rc;
     h->res_cap = records;
     return SLAM_OK;
 }
@@ -203,7 +173,7 @@ int slam_pfb_create(const slam_pf_config* cfgs, int32_t n_filters, int32_t n_par
         f.ess_th = cfgs[b].ess_threshold;
     }
     std::vector<int32_t> leaves, ops;
-    if (n_particles >= 8) build_tree(0, n_particles, leaves, ops);
+    if (n_particles >= 8) pairwise_sum_split(0, n_particles, leaves, ops);
     SLAM_ARG_CHECK(leaves.size() / 2 <= (size_t)kPfbMaxLeaves && ops.size() <= 2 * (size_t)kPfbMaxLeaves,
                    "slam_pfb_create: np.sum tree larger than the kernel's table");
 
@@ -211,7 +181,8 @@ int slam_pfb_create(const slam_pf_config* cfgs, int32_t n_filters, int32_t n_par
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev, "slam_pfb_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_pfb* h = new slam_pfb();
+    HandlePtr<slam_pfb, slam_pfb_destroy> hp(new slam_pfb());
+    slam_pfb* h = hp.get();
     h->device = device;
     h->B = n_filters;
     h->n = n_particles;
@@ -224,57 +195,49 @@ int slam_pfb_create(const slam_pf_config* cfgs, int32_t n_filters, int32_t n_par
     h->nops = (int32_t)ops.size();
     const size_t B = (size_t)n_filters, n = (size_t)n_particles, npad = (size_t)h->npad;
     const size_t nl2 = 2 * (size_t)n_landmarks;
-    int rc = SLAM_OK;
-    auto body = [&]() -> int {
-        SLAM_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        SLAM_HIP_TRY(hipEventCreate(&h->ev0));
-        SLAM_HIP_TRY(hipEventCreate(&h->ev1));
-        int r;
-        for (int k = 0; k < 2; ++k)
-            if ((r = dalloc(h, &h->x[k], B * npad)) || (r = dalloc(h, &h->y[k], B * npad)) ||
-                (r = dalloc(h, &h->th[k], B * npad)))
-                return r;
-        if ((r = dalloc(h, &h->w_un, B * npad)) || (r = dalloc(h, &h->s_cur, B)) ||
-            (r = dalloc(h, &h->c, B * npad)) || (r = dalloc(h, &h->spec, B * n)) ||
-            (r = dalloc(h, &h->flags, B)) || (r = dalloc(h, &h->filt, B)) ||
-            (r = dalloc(h, &h->lm, B * nl2)) || (r = dalloc(h, &h->leaves, leaves.size() + 2)) ||
-            (r = dalloc(h, &h->ops, ops.size() + 1)) || (r = dalloc(h, &h->ctl1, 2 * B)) ||
-            (r = dalloc(h, &h->z1, B * nl2)) || (r = dalloc(h, &h->noise, 3 * B * n)) ||
-            (r = dalloc(h, &h->ofs, B)) || (r = dalloc(h, &h->idx, B * n)) ||
-            (r = dalloc(h, &h->istat, B)) || (r = dalloc(h, &h->ispec, B)))
+    SLAM_HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    DeviceMem& m = h->mem;
+    int r;
+    if ((r = m.event(&h->ev0)) || (r = m.event(&h->ev1))) return r;
+    for (int k = 0; k < 2; ++k)
+        if ((r = m.alloc(&h->x[k], B * npad)) || (r = m.alloc(&h->y[k], B * npad)) ||
+            (r = m.alloc(&h->th[k], B * npad)))
             return r;
-        if ((r = ensure_results(h, B))) return r;
-        // initial state: particle_filter.py:81-84 (pad slots: zero state, zero weight)
-        std::vector<double> row(B * npad, 0.0);
-        for (int q = 0; q < 3; ++q) {
-            for (size_t b = 0; b < B; ++b)
-                std::fill(row.begin() + b * npad, row.begin() + b * npad + n, cfgs[b].x0[q]);
-            double* d0 = q == 0 ? h->x[0] : q == 1 ? h->y[0] : h->th[0];
-            double* d1 = q == 0 ? h->x[1] : q == 1 ? h->y[1] : h->th[1];
-            SLAM_HIP_TRY(hipMemcpy(d0, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
-            SLAM_HIP_TRY(hipMemcpy(d1, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
-        }
-        std::fill(row.begin(), row.end(), 0.0);
+    if ((r = m.alloc(&h->w_un, B * npad)) || (r = m.alloc(&h->s_cur, B)) ||
+        (r = m.alloc(&h->c, B * npad)) || (r = m.alloc(&h->spec, B * n)) ||
+        (r = m.alloc(&h->flags, B)) || (r = m.alloc(&h->filt, B)) ||
+        (r = m.alloc(&h->lm, B * nl2)) || (r = m.alloc(&h->leaves, leaves.size() + 2)) ||
+        (r = m.alloc(&h->ops, ops.size() + 1)) || (r = m.alloc(&h->ctl1, 2 * B)) ||
+        (r = m.alloc(&h->z1, B * nl2)) || (r = m.alloc(&h->noise, 3 * B * n)) ||
+        (r = m.alloc(&h->ofs, B)) || (r = m.alloc(&h->idx, B * n)) ||
+        (r = m.alloc(&h->istat, B)) || (r = m.alloc(&h->ispec, B)))
+        return r;
+    if ((r = ensure_results(h, B))) return r;
+    // initial state: particle_filter.py:81-84 (pad slots: zero state, zero weight)
+    std::vector<double> row(B * npad, 0.0);
+    for (int q = 0; q < 3; ++q) {
         for (size_t b = 0; b < B; ++b)
-            std::fill(row.begin() + b * npad, row.begin() + b * npad + n, 1.0 / (double)n_particles);
-        SLAM_HIP_TRY(hipMemcpy(h->w_un, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
-        SLAM_HIP_TRY(hipMemset(h->c, 0, sizeof(uint64_t) * B * npad));
-        std::vector<double> ones(B, 1.0);
-        SLAM_HIP_TRY(hipMemcpy(h->s_cur, ones.data(), sizeof(double) * B, hipMemcpyHostToDevice));
-        SLAM_HIP_TRY(hipMemset(h->flags, 0, sizeof(int32_t) * B));
-        SLAM_HIP_TRY(hipMemcpy(h->filt, filt.data(), sizeof(PfbFilter) * B, hipMemcpyHostToDevice));
-        SLAM_HIP_TRY(hipMemcpy(h->lm, landmarks, sizeof(double) * B * nl2, hipMemcpyHostToDevice));
-        if (!leaves.empty()) {
-            SLAM_HIP_TRY(hipMemcpy(h->leaves, leaves.data(), leaves.size() * 4, hipMemcpyHostToDevice));
-            SLAM_HIP_TRY(hipMemcpy(h->ops, ops.data(), ops.size() * 4, hipMemcpyHostToDevice));
-        }
-        return SLAM_OK;
-    };
-    if ((rc = body())) {
-        slam_pfb_destroy(h);
-        return rc;
+            std::fill(row.begin() + b * npad, row.begin() + b * npad + n, cfgs[b].x0[q]);
+        double* d0 = q == 0 ? h->x[0] : q == 1 ? h->y[0] : h->th[0];
+        double* d1 = q == 0 ? h->x[1] : q == 1 ? h->y[1] : h->th[1];
+        SLAM_HIP_TRY(hipMemcpy(d0, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
+        SLAM_HIP_TRY(hipMemcpy(d1, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
     }
-    *out = h;
+    std::fill(row.begin(), row.end(), 0.0);
+    for (size_t b = 0; b < B; ++b)
+        std::fill(row.begin() + b * npad, row.begin() + b * npad + n, 1.0 / (double)n_particles);
+    SLAM_HIP_TRY(hipMemcpy(h->w_un, row.data(), sizeof(double) * B * npad, hipMemcpyHostToDevice));
+    SLAM_HIP_TRY(hipMemset(h->c, 0, sizeof(uint64_t) * B * npad));
+    std::vector<double> ones(B, 1.0);
+    SLAM_HIP_TRY(hipMemcpy(h->s_cur, ones.data(), sizeof(double) * B, hipMemcpyHostToDevice));
+    SLAM_HIP_TRY(hipMemset(h->flags, 0, sizeof(int32_t) * B));
+    SLAM_HIP_TRY(hipMemcpy(h->filt, filt.data(), sizeof(PfbFilter) * B, hipMemcpyHostToDevice));
+    SLAM_HIP_TRY(hipMemcpy(h->lm, landmarks, sizeof(double) * B * nl2, hipMemcpyHostToDevice));
+    if (!leaves.empty()) {
+        SLAM_HIP_TRY(hipMemcpy(h->leaves, leaves.data(), leaves.size() * 4, hipMemcpyHostToDevice));
+        SLAM_HIP_TRY(hipMemcpy(h->ops, ops.data(), ops.size() * 4, hipMemcpyHostToDevice));
+    }
+    *out = hp.release();
     return SLAM_OK;
 }
 
@@ -282,10 +245,6 @@ int slam_pfb_destroy(slam_pfb* h) {
     if (!h) return SLAM_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : h->allocs) (void)hipFree(p);
-    if (h->res_host) (void)hipHostFree(h->res_host);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SLAM_OK;
@@ -428,10 +387,9 @@ int slam_pfb_load_observations(slam_pfb* h, int32_t n_steps, const double* z_all
     SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t per = 2 * (size_t)h->B * h->nl;
     if (n_steps > h->z_steps) {
-        release(h, h->z_all);
-        h->z_all = nullptr;
+        h->mem.release(h->z_all);
         h->z_steps = 0;
-        const int rc = dalloc(h, &h->z_all, per * n_steps);
+        const int rc = h->mem.alloc(&h->z_all, per * n_steps);
         if (rc) return rc;
     }
     SLAM_HIP_TRY(hipMemcpy(h->z_all, z_all, sizeof(double) * per * n_steps, hipMemcpyHostToDevice));
@@ -449,10 +407,9 @@ int slam_pfb_run(slam_pfb* h, int32_t first_step, int32_t n_steps, const double*
     int rc;
     if (n_steps > h->ctl_cap) {
         SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
-        release(h, h->ctl);
-        h->ctl = nullptr;
+        h->mem.release(h->ctl);
         h->ctl_cap = 0;
-        if ((rc = dalloc(h, &h->ctl, 2 * B * n_steps))) return rc;
+        if ((rc = h->mem.alloc(&h->ctl, 2 * B * n_steps))) return rc;
         h->ctl_cap = n_steps;
     }
     if ((rc = ensure_results(h, B * n_steps))) return rc;

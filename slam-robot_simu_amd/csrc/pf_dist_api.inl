@@ -23,8 +23,8 @@ struct slam_dist {
     std::vector<int64_t*> hi;
     std::vector<int32_t*> bsel, bsel_off;
     std::vector<unsigned*> tk;                // 4 ticket blocks per held shard
-    std::vector<void*> dallocs;
-    std::vector<void*> opened;                // IPC mappings of peer regions
+    DeviceMem mem;
+    std::vector<void*> opened;               // IPC mappings of peer regions
     hipStream_t stream = nullptr;             // LOCAL: the shared stream
     bool connected = false;
     bool merged = false;                      // one-launch resample exchange (one held shard, co-resident grid)
@@ -41,12 +41,6 @@ struct slam_dist {
 };
 
 namespace {
-
-int dist_alloc(slam_dist* d, void** p, size_t bytes) {
-    SLAM_HIP_TRY(hipMalloc(p, bytes ? bytes : 8));
-    d->dallocs.push_back(*p);
-    return SLAM_OK;
-}
 
 void dist_drop_graphs(slam_dist* d) {
     for (auto* gs : {d->graph, d->graph1})
@@ -405,25 +399,15 @@ int slam_dist_create(slam_pf** shards, int32_t n_held, int32_t world, int32_t ra
     if (n_held == world)
         SLAM_ARG_CHECK(shards[n_held - 1]->gbase + shards[n_held - 1]->n == N,
                        "slam_dist_create: the shards do not cover the filter");
-    slam_dist* d = new slam_dist();
+    HandlePtr<slam_dist, slam_dist_destroy> dp(new slam_dist());
+    slam_dist* d = dp.get();
     d->world = world;
     d->rank0 = rank0;
     d->nloc = n_held;
     d->local = (n_held == world);
     d->device = shards[0]->device;
     d->sh.assign(shards, shards + n_held);
-    // every failure from here on releases d and what it holds (slam_dist_destroy)
-    auto bail = [&](int rc) {
-        slam_dist_destroy(d);
-        return rc;
-    };
-#define DIST_TRY(expr)                                                                    \
-    do {                                                                                  \
-        const hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess)                                                             \
-            return bail(fail(SLAM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
-    } while (0)
-    DIST_TRY(hipSetDevice(d->device));
+    SLAM_HIP_TRY(hipSetDevice(d->device));
     // the largest shard sets the slot sizes (shards are equal but the last);
     // every rank must lay its region out the same way, so one shard per
     // process takes the standard split's full shard (rank 0's: ceil(N / world)
@@ -458,43 +442,47 @@ int slam_dist_create(slam_pf** shards, int32_t n_held, int32_t world, int32_t ra
     int rc;
     if (d->local) {
         hipError_t e = hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) return bail(fail(SLAM_ERR_HIP, "slam_dist_create: stream creation failed"));
+        if (e != hipSuccess) return fail(SLAM_ERR_HIP, "slam_dist_create: stream creation failed");
     }
+    DeviceMem& m = d->mem;
     for (int i = 0; i < n_held; ++i) {
         slam_pf* h = d->sh[i];
-        if (d->local && (rc = slam_pf_set_stream(h, d->stream, 1))) return bail(rc);
-        void* xb = nullptr;
-        if (hipExtMallocWithFlags(&xb, (size_t)L.total, hipDeviceMallocFinegrained) != hipSuccess)
-            return bail(fail(SLAM_ERR_HIP, "slam_dist_create: fine-grained exchange region allocation failed"));
-        d->xbuf.push_back((char*)xb);
-        DIST_TRY(hipMemset(xb, 0, (size_t)L.flags + 3 * kDistMaxWorld * 8));
+        if (d->local && (rc = slam_pf_set_stream(h, d->stream, 1))) return rc;
+        char* xb = nullptr;
+        if (m.alloc(&xb, (size_t)L.total, hipDeviceMallocFinegrained))
+            return fail(SLAM_ERR_HIP, "slam_dist_create: fine-grained exchange region allocation failed");
+        d->xbuf.push_back(xb);
+        SLAM_HIP_TRY(hipMemset(xb, 0, (size_t)L.flags + 3 * kDistMaxWorld * 8));
         // run tags (epoch >= 1) of the merged exchange start unmatched
-        DIST_TRY(hipMemset((char*)xb + L.pitem, 0, (size_t)(L.total - L.pitem)));
-        void *p1, *p2, *p3, *p4, *p5, *p6, *p7, *p8;
+        SLAM_HIP_TRY(hipMemset(xb + L.pitem, 0, (size_t)(L.total - L.pitem)));
+        DistScratch* scr;
+        SpecialIn* spec_g;
+        SpecialOut* spec_go;
+        int64_t* hi;
+        int32_t *bsel, *bsel_off;
+        unsigned* tk;
+        DistItem* self_items;
         const int32_t nbs = h->nb_scan;
-        if ((rc = dist_alloc(d, &p1, sizeof(DistScratch))) ||
-            (rc = dist_alloc(d, &p2, sizeof(SpecialIn) * (size_t)std::max<int64_t>(N, 1))) ||
-            (rc = dist_alloc(d, &p3, sizeof(SpecialOut) * (size_t)std::max<int64_t>(N, 1))) ||
-            (rc = dist_alloc(d, &p4, sizeof(int64_t) * (size_t)h->n)) ||
-            (rc = dist_alloc(d, &p5, sizeof(int32_t) * (size_t)nbs)) ||
-            (rc = dist_alloc(d, &p6, sizeof(int32_t) * (size_t)nbs)) ||
-            (rc = dist_alloc(d, &p7, sizeof(unsigned) * 4 * kTicketWords)) ||
-            (rc = dist_alloc(d, &p8, sizeof(DistItem) * (size_t)L.cap_item)))
-            return bail(rc);
-        DIST_TRY(hipMemset(p1, 0, sizeof(DistScratch)));
-        DIST_TRY(hipMemset(p7, 0, sizeof(unsigned) * 4 * kTicketWords));
-        d->scr.push_back((DistScratch*)p1);
-        d->spec_g.push_back((SpecialIn*)p2);
-        d->spec_go.push_back((SpecialOut*)p3);
-        d->hi.push_back((int64_t*)p4);
-        d->bsel.push_back((int32_t*)p5);
-        d->bsel_off.push_back((int32_t*)p6);
-        d->tk.push_back((unsigned*)p7);
+        if ((rc = m.alloc(&scr, 1)) || (rc = m.alloc(&spec_g, (size_t)std::max<int64_t>(N, 1))) ||
+            (rc = m.alloc(&spec_go, (size_t)std::max<int64_t>(N, 1))) ||
+            (rc = m.alloc(&hi, (size_t)h->n)) || (rc = m.alloc(&bsel, (size_t)nbs)) ||
+            (rc = m.alloc(&bsel_off, (size_t)nbs)) || (rc = m.alloc(&tk, 4 * kTicketWords)) ||
+            (rc = m.alloc(&self_items, (size_t)L.cap_item)))
+            return rc;
+        SLAM_HIP_TRY(hipMemset(scr, 0, sizeof(DistScratch)));
+        SLAM_HIP_TRY(hipMemset(tk, 0, sizeof(unsigned) * 4 * kTicketWords));
+        d->scr.push_back(scr);
+        d->spec_g.push_back(spec_g);
+        d->spec_go.push_back(spec_go);
+        d->hi.push_back(hi);
+        d->bsel.push_back(bsel);
+        d->bsel_off.push_back(bsel_off);
+        d->tk.push_back(tk);
         DistPeers P{};
         P.world = world;
         P.rank = rank0 + i;
         P.L = L;
-        P.self_items = (DistItem*)p8;
+        P.self_items = self_items;
         d->peers.push_back(P);
     }
     // shard bases.  LOCAL: the handles'.  One shard per process: the standard
@@ -510,7 +498,7 @@ int slam_dist_create(slam_pf** shards, int32_t n_held, int32_t world, int32_t ra
         int64_t g0 = 0, nl = 0;
         slam_dist_shard_range(N, world, rank0, &g0, &nl);
         if (d->sh[0]->gbase != g0 || d->sh[0]->n != nl)
-            return bail(fail(SLAM_ERR_ARG, "slam_dist_create: shard is not slam_dist_shard_range's for its rank"));
+            return fail(SLAM_ERR_ARG, "slam_dist_create: shard is not slam_dist_shard_range's for its rank");
     }
     gb[world] = N;
     {
@@ -528,14 +516,13 @@ int slam_dist_create(slam_pf** shards, int32_t n_held, int32_t world, int32_t ra
     }
     for (auto& P : d->peers)
         for (int q = 0; q <= world; ++q) P.gb[q] = gb[q];
-    DIST_TRY(hipDeviceSynchronize());
-#undef DIST_TRY
+    SLAM_HIP_TRY(hipDeviceSynchronize());
     if (d->local) {
         for (auto& P : d->peers)
             for (int q = 0; q < world; ++q) P.base[q] = d->xbuf[q];
         d->connected = true;
     }
-    *out = d;
+    *out = dp.release();
     return SLAM_OK;
 }
 
@@ -647,19 +634,14 @@ int slam_dist_set_collective(slam_dist* d, slam_comm* comm) {
     dist_drop_graphs(d);
     const int w = d->world;
     if (!d->cnt_mat) {
-        void* p = nullptr;
-        int rc = dist_alloc(d, &p, 8 * (size_t)w * w);
-        if (rc) return rc;
-        d->cnt_mat = (int64_t*)p;
-        SLAM_HIP_TRY(hipHostMalloc((void**)&d->hst, 8 * (size_t)(3 * w * w + 16)));
-        for (int i = 0; i < d->nloc; ++i) {
-            void *io = nullptr, *co = nullptr;
-            if ((rc = dist_alloc(d, &io, sizeof(DistItem) * (size_t)w * (size_t)d->L.cap_item)) ||
-                (rc = dist_alloc(d, &co, 8 * (size_t)w)))
+        int rc;
+        if ((rc = d->mem.alloc(&d->cnt_mat, (size_t)w * w)) ||
+            (rc = d->mem.alloc_pinned(&d->hst, nullptr, (size_t)(3 * w * w + 16), hipHostMallocDefault)))
+            return rc;
+        for (int i = 0; i < d->nloc; ++i)
+            if ((rc = d->mem.alloc(&d->peers[i].item_out, (size_t)w * (size_t)d->L.cap_item)) ||
+                (rc = d->mem.alloc(&d->peers[i].cnt_out, (size_t)w)))
                 return rc;
-            d->peers[i].item_out = (DistItem*)io;
-            d->peers[i].cnt_out = (int64_t*)co;
-        }
     }
     for (int i = 0; i < d->nloc; ++i) {
         DistPeers& P = d->peers[i];
@@ -684,9 +666,6 @@ int slam_dist_destroy(slam_dist* d) {
         if (h && h->stream) (void)hipStreamSynchronize(h->stream);
     dist_drop_graphs(d);
     for (void* p : d->opened) (void)hipIpcCloseMemHandle(p);
-    if (d->hst) (void)hipHostFree(d->hst);
-    for (char* p : d->xbuf) (void)hipFree(p);
-    for (void* p : d->dallocs) (void)hipFree(p);
     // LOCAL: the shards keep running on private streams again
     if (d->local)
         for (auto* h : d->sh)

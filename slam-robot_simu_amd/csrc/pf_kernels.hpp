@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <limits>
+#include <vector>
 
 #include "common.hpp"
 
@@ -281,6 +282,23 @@ __host__ __device__ inline DDSum closed_lane_partial(const int k, const int lane
     for (int32_t j = lane; j < nl; j += kClosedLanes)
         closed_term(S, k, lm[2 * j], lm[2 * j + 1], z[2 * j], z[2 * j + 1]);
     return S;
+}
+
+// numpy's pairwise-sum split of n elements from lo (one np.sum buffer, n <=
+// kSumChunk): leaves (lo, count) of at most 128 elements + the post-order
+// program that adds them (a leaf's index, or -1: add the two on top)
+inline void pairwise_sum_split(int lo, int n, std::vector<int32_t>& leaves, std::vector<int32_t>& ops) {
+    if (n <= 128) {
+        ops.push_back((int32_t)(leaves.size() / 2));
+        leaves.push_back(lo);
+        leaves.push_back(n);
+        return;
+    }
+    int h = n / 2;
+    h -= h % 8;
+    pairwise_sum_split(lo, h, leaves, ops);
+    pairwise_sum_split(lo + h, n - h, leaves, ops);
+    ops.push_back(-1);
 }
 
 }  // namespace slam

@@ -638,13 +638,6 @@ int glibc_log_table(GlibcLogTable* out) {
     return SLAM_OK;
 }
 
-void mt_free(MtBuffers& b) {
-    void* ps[] = {b.st, b.tab, b.X, b.seg, b.q, b.bcnt, b.bpre, b.normals, b.pre};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    b = MtBuffers{};
-}
-
 namespace {
 
 size_t round_lds_bytes(int32_t R) {
@@ -677,7 +670,7 @@ int mt_reserve(MtBuffers& b, int64_t g_cap, int64_t pre_cap, int device) {
     GlibcLogTable T;
     rc = glibc_log_table(&T);
     if (rc) return rc;
-    mt_free(b);
+    b.reset();
     b.device = device;
     b.g_cap = g_cap;
     b.pre_cap = pre_cap;
@@ -717,15 +710,18 @@ int mt_reserve(MtBuffers& b, int64_t g_cap, int64_t pre_cap, int device) {
     const int64_t live = live_words(b.S);
     b.cap = 1;
     while (b.cap < live) b.cap <<= 1;                    // a power of two: index & (cap - 1)
-    SLAM_HIP_TRY(hipMalloc(&b.st, sizeof(MtDeviceState)));
-    SLAM_HIP_TRY(hipMalloc(&b.tab, sizeof(GlibcLogTable)));
-    SLAM_HIP_TRY(hipMalloc(&b.X, sizeof(uint32_t) * (size_t)b.cap));
-    SLAM_HIP_TRY(hipMalloc(&b.seg, sizeof(uint32_t) * kMtN * (size_t)b.R));
-    SLAM_HIP_TRY(hipMalloc(&b.q, sizeof(uint32_t) * (kMtDeg / 2 + 16)));
-    SLAM_HIP_TRY(hipMalloc(&b.bcnt, sizeof(unsigned) * (size_t)std::max<int64_t>(b.nb_count, 1)));
-    SLAM_HIP_TRY(hipMalloc(&b.bpre, sizeof(unsigned) * (size_t)(b.nb_count + 1)));
-    SLAM_HIP_TRY(hipMalloc(&b.normals, sizeof(double) * (size_t)std::max<int64_t>(g_cap, 1)));
-    SLAM_HIP_TRY(hipMalloc(&b.pre, sizeof(double) * (size_t)std::max<int64_t>(pre_cap, 1)));
+    // a failure here leaves b.st set with the capacities of this attempt: reset
+    // on the way out, so the next reserve starts from nothing
+    DeviceMem& m = b.mem;
+    if ((rc = m.alloc(&b.st, 1)) || (rc = m.alloc(&b.tab, 1)) || (rc = m.alloc(&b.X, (size_t)b.cap)) ||
+        (rc = m.alloc(&b.seg, kMtN * (size_t)b.R)) || (rc = m.alloc(&b.q, kMtDeg / 2 + 16)) ||
+        (rc = m.alloc(&b.bcnt, (size_t)std::max<int64_t>(b.nb_count, 1))) ||
+        (rc = m.alloc(&b.bpre, (size_t)(b.nb_count + 1))) ||
+        (rc = m.alloc(&b.normals, (size_t)std::max<int64_t>(g_cap, 1))) ||
+        (rc = m.alloc(&b.pre, (size_t)std::max<int64_t>(pre_cap, 1)))) {
+        b.reset();
+        return rc;
+    }
     SLAM_HIP_TRY(hipMemcpy(b.tab, &T, sizeof(T), hipMemcpyHostToDevice));
     b.n_idx = 0;
     if (b.R > 1) {
@@ -853,6 +849,7 @@ struct slam_mt {
     int device = 0;
     hipStream_t stream = nullptr;
     MtBuffers b;
+    DeviceMem mem;
     int32_t* status = nullptr;
 };
 
@@ -879,23 +876,17 @@ int slam_mt_create(const uint32_t* key, int32_t pos, int32_t has_gauss, double g
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev, "slam_mt_create: no such HIP device");
     SLAM_HIP_TRY(hipSetDevice(device));
-    slam_mt* h = new slam_mt;
+    HandlePtr<slam_mt, slam_mt_destroy> hp(new slam_mt);
+    slam_mt* h = hp.get();
     h->device = device;
-    int rc;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->status, sizeof(int32_t)) != hipSuccess) {
-        rc = fail(SLAM_ERR_HIP, "slam_mt_create: stream / status allocation failed");
-    } else if ((rc = mt_reserve(h->b, 1, 1, device)) == SLAM_OK) {
-        rc = mt_set_state(h->b, key, pos, has_gauss, gauss, h->stream);
-    }
-    if (rc) {
-        mt_free(h->b);
-        if (h->status) (void)hipFree(h->status);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-        delete h;
+        h->mem.alloc(&h->status, 1) != SLAM_OK)
+        return fail(SLAM_ERR_HIP, "slam_mt_create: stream / status allocation failed");
+    int rc;
+    if ((rc = mt_reserve(h->b, 1, 1, device)) ||
+        (rc = mt_set_state(h->b, key, pos, has_gauss, gauss, h->stream)))
         return rc;
-    }
-    *out = h;
+    *out = hp.release();
     return SLAM_OK;
 }
 
@@ -903,8 +894,6 @@ int slam_mt_destroy(slam_mt* h) {
     if (!h) return SLAM_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    mt_free(h->b);
-    if (h->status) (void)hipFree(h->status);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return SLAM_OK;

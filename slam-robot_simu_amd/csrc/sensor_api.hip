@@ -13,9 +13,7 @@
 // cos / sin of the robot yaw come from the caller (NumPy's, one per pose), so
 // the rotation is the reference's to the rounding of its 2x2 product; the
 // direction is the device atan2 (within an ulp of the C library's).
-#include <mutex>
-
-#include "common.hpp"
+#include "device_mem.hpp"
 
 namespace slam {
 
@@ -58,32 +56,15 @@ __global__ __launch_bounds__(256) void scan_noise_kernel(const int64_t n,
 
 namespace {
 
-struct SensorScratch {
-    std::mutex mu;
-    size_t cap = 0;      // bytes
-    char* buf = nullptr;
-    hipStream_t stream = nullptr;
-};
+using SensorScratch = StaticScratch;      // cap in bytes
 
-SensorScratch& sensor_scratch(int device) {
-    static SensorScratch s[64];
-    return s[device & 63];
-}
+SensorScratch& sensor_scratch(int device) { return static_scratch<struct SensorTag>(device); }
 
 int sensor_begin(SensorScratch& sc, int device, size_t bytes) {
     int ndev = 0;
     SLAM_HIP_TRY(hipGetDeviceCount(&ndev));
     SLAM_ARG_CHECK(device >= 0 && device < ndev && device < 64, "scan sensor: no such HIP device");
-    SLAM_HIP_TRY(hipSetDevice(device));
-    if (!sc.stream) SLAM_HIP_TRY(hipStreamCreateWithFlags(&sc.stream, hipStreamNonBlocking));
-    if (bytes > sc.cap) {
-        if (sc.buf) (void)hipFree(sc.buf);
-        sc.buf = nullptr;
-        sc.cap = 0;
-        SLAM_HIP_TRY(hipMalloc(&sc.buf, bytes));
-        sc.cap = bytes;
-    }
-    return SLAM_OK;
+    return sc.begin(device, bytes, 1);
 }
 
 size_t al256(size_t b) { return (b + 255) / 256 * 256; }

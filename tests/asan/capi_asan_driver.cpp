@@ -197,6 +197,14 @@ int main() {
     }
     EXPECT_ERR(slam_glibc_log(4, nullptr, y.data()));
 
+    // ---- after every failed create above: nothing is left behind
+    EXPECT_ERR(slam_debug_live_resources(nullptr));
+    int64_t live[3] = {-1, -1, -1};
+    CHECK(slam_debug_live_resources(live) == 0, "live_resources: %s", slam_last_error());
+    CHECK(live[0] == 0 && live[1] == 0 && live[2] == 0,
+          "live resources at the end: %lld device bytes, %lld pinned bytes, %lld events",
+          (long long)live[0], (long long)live[1], (long long)live[2]);
+
     std::printf("capi_asan_driver: %d checks, %d failed\n", g_checks, g_fail);
     return g_fail ? 1 : 0;
 }
