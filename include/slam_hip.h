@@ -584,6 +584,77 @@ int slam_fs_get_counts(slam_fs* h, int32_t* counts);
  * unless the handle was created with record != 0. */
 int slam_fs_get_assoc(slam_fs* h, int32_t* out);
 
+/* --------------------------------------------------------------------
+ * FastSLAM 2.0: poses drawn from the observation-informed proposal.  A
+ * proposal handle has known data association and SLAM_MOTION_LINEAR; instead
+ * of drawing the pose from the motion model alone and weighing it against the
+ * scan afterwards, every particle filters its pose through the step's scan
+ * first and draws from the result.  Q = F^T F of cfg.pf.q_factor,
+ * Q[i][j] = sum_k F[3k+i] F[3k+j] (k ascending), formed once at create.
+ *
+ * One step:
+ *   1. resample: exactly as on a known-association handle;
+ *   2. proposal, per particle: mu = the noise-free linear motion of the pose
+ *      (x + v (dt cos th), y + v (dt sin th), wrap(th + omega dt)), Sigma = Q
+ *      (six entries, symmetric), L = 0; then for each observation t in the order
+ *      given (landmark j, z = (d, phi, psi)):
+ *      orientation (use_orient; seen landmark or not):
+ *        e = wrap(psi - wrap(pi/2 - mu_th)), s_o = Sigma_thth + vo
+ *        (vo = r_dir^2 + r_orient^2), L -= (e^2 / s_o + ln s_o) / 2, and the
+ *        scalar Kalman update with H = (0, 0, -1): col = Sigma[:, th],
+ *        k = col / s_o, mu -= k e, Sigma_ab -= k_a col_b (a <= b);
+ *      j unseen: nothing more (a first sighting carries no pose information);
+ *      j seen: linearised at the current mu and the landmark's prior (m_j, P_j):
+ *        dx, dy, q, r, bearing, H_m and R as in step 3 of the 1.0 update with the
+ *        pose mu; H_x = [-H_m | (0, -1)^T] (2 x 3); A = Sigma H_x^T (3 x 2);
+ *        S = H_m P_j H_m^T + R + H_x A (S_01 from row 0 of H_x);
+ *        e = (d - r, wrap(phi - bearing)); L -= (e^T S^-1 e + ln det S) / 2;
+ *        K = A S^-1 through the 2 x 2 adjugate; mu += K e;
+ *        Sigma_ab -= K_a0 A_b0 + K_a1 A_b1 (a <= b);
+ *   3. sample: Lc = the lower Cholesky factor of Sigma (l00 = sqrt(S00),
+ *      l10 = S01 / l00, l20 = S02 / l00, l11 = sqrt(S11 - l10^2),
+ *      l21 = (S12 - l20 l10) / l11, l22 = sqrt(S22 - l20^2 - l21^2)); the pose is
+ *      mu + Lc xi, theta not wrapped (as slam_pf).  noise non-NULL:
+ *      xi = noise[p][0..2] -- three STANDARD normals per particle, not the
+ *      Q-shaped noise a 1.0 handle takes.  noise NULL: the three normals the
+ *      handle's predict would have given the particle at this step (particle 2p
+ *      the first three, 2p + 1 the last three of its pair's six); the step
+ *      counter advances as in a 1.0 step.  A non-positive pivot is not guarded:
+ *      it gives NaN, as any degenerate input;
+ *   4. maps, at the sampled pose and per observation in order: the first-sighting
+ *      initialisation or the EKF update of step 3 of the 1.0 contract, without
+ *      its weight term; then the landmarks are marked seen;
+ *   5. w_un = w exp(L - max_p L) and the step end, unchanged.
+ * With k = 0 a step is mu + chol(Q) xi with all weights kept.
+ *
+ * The copies of a resampled particle share mu, Sigma and L, so in the step
+ * after a resampling they carry bit-equal weights (the pose noise no longer
+ * enters the weight); max_idx is then the first of equals, as np.argmax.
+ *
+ * slam_fs_step, slam_fs_load_observations / slam_fs_run, slam_fs_resample, the
+ * state and map accessors, slam_fs_info and slam_fs_timing work as on a
+ * known-association handle.  One launch does steps 2 to 4, so slam_fs_timing's
+ * out[1] is motion + proposal + sampling + map update and out[2] the weights
+ * alone.  slam_fs_predict and slam_fs_update return SLAM_ERR_ARG: the proposal
+ * needs the step's control and scan together.
+ * -------------------------------------------------------------------- */
+typedef struct {
+    int32_t record;       /* keep each step's mu, Sigma for slam_fs_get_proposal
+                             (72 B x n_particles written per step) */
+    int32_t pad0;
+} slam_fs_proposal_config;
+
+/* slam_fs_create's rules; in addition SLAM_ERR_ARG before any HIP call for a
+ * NULL cfg, pcfg or out and for cfg->pf.motion != SLAM_MOTION_LINEAR (the
+ * velocity model needs a per-particle V M V^T). */
+int slam_fs_create_proposal(const slam_fs_config* cfg, const slam_fs_proposal_config* pcfg,
+                            int64_t n_particles, int32_t n_landmarks, int device, slam_fs** out);
+/* The last step's mu, Sigma and L before sampling: mean[NP][3], cov[NP][6]
+ * (00 01 02 11 12 22), L[NP]; any pointer may be NULL.  SLAM_ERR_ARG unless the
+ * handle was created by slam_fs_create_proposal with record != 0 and has
+ * stepped. */
+int slam_fs_get_proposal(slam_fs* h, double* mean, double* cov, double* L);
+
 /* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve
  * (graph_based_slam.py: setPairObs :362-439, updateEstPose :452-514) and

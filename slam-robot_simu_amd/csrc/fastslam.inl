@@ -1,7 +1,8 @@
 // fastslam.inl -- gfx950 kernels of FastSLAM 1.0 with known data association
 // (included by fs_api.inl): the per-particle landmark EKFs with their log
 // weights, the weight pass, and the resampling gather of whole maps; below
-// them the kernels of per-particle maximum-likelihood association.
+// them the kernels of per-particle maximum-likelihood association, and last
+// the one kernel of FastSLAM 2.0's observation-informed proposal.
 //
 // Map layout: component-major per landmark,
 //     map[(5 j + c) * npad + p],   c = mx, my, pxx, pxy, pyy
@@ -468,5 +469,250 @@ __global__ __launch_bounds__(kFsThreads) void fs_assoc_pack_kernel(
             out[((size_t)(p - p0) * nl + j) * ncomp + c] =
                 j < cp ? map[((size_t)kFsComp * j + comp0 + c) * (size_t)npad + (size_t)p] : NAN;
 }
+
+// ------------------------------------------------------------------------
+// FastSLAM 2.0: the pose is drawn from the proposal that has seen
+// the step's scan.  Known association, linear motion.
+// ------------------------------------------------------------------------
+struct FsPropQ {
+    double q00, q01, q02, q11, q12, q22;    // Q = F^T F of the handle's q_factor
+};
+
+// The block's next kFsObsLds observations into LDS (every lane reaches both barriers)
+#define SLAM_FS_STAGE_OBS(base, cnt)                                                             \
+    __syncthreads();                                                                             \
+    if ((int32_t)threadIdx.x < (cnt)) {                                                          \
+        const FsObs o = obs[(base) + threadIdx.x];                                               \
+        s_d[threadIdx.x] = o.d;                                                                  \
+        s_phi[threadIdx.x] = o.phi;                                                              \
+        s_psi[threadIdx.x] = o.psi;                                                              \
+        s_r0[threadIdx.x] = o.r0;                                                                \
+        s_r1[threadIdx.x] = o.r1;                                                                \
+        s_rx[threadIdx.x] = o.rx;                                                                \
+        s_ry[threadIdx.x] = o.ry;                                                                \
+        s_vo[threadIdx.x] = o.vo;                                                                \
+        s_id[threadIdx.x] = o.id;                                                                \
+        s_seen[threadIdx.x] = seen[o.id];                                                        \
+    }                                                                                            \
+    __syncthreads();
+
+// One lane per particle, one launch, two passes over the step's observations.
+// Pass 1 runs a three-state Kalman filter on the pose: from the noise-free
+// motion with covariance Q through the orientation of every observation and
+// the range and bearing of every seen landmark (linearised at the current
+// mean and the landmark's prior), collecting the log weight L on the way.  The
+// pose is then mean + chol(cov) xi.  Pass 2 is fs_update_kernel's map update
+// at that pose (its expressions restated line by line, without the weight
+// term).  xi: noise[p][0..2] (HOSTNOISE) or the particle's half of its pair's
+// device normals, as the fused kernel deals them.  The poses go to the other
+// ping-pong half; the previous weights are normalised in place (w_un / s, as
+// the 1.0 predict leaves them).  rec (NULL unless recorded): [9][npad], the
+// mean and the covariance (00 01 02 11 12 22) before sampling.
+// Three waves per SIMD (168 VGPRs, no scratch), as fs_update_kernel; held to
+// four the compiler spills 22 to 90 registers.
+template <bool HOSTNOISE>
+__global__ __launch_bounds__(kFsThreads) void
+fs_proposal_kernel(const int64_t n, const int64_t npad, const double* __restrict__ xs,
+                   const double* __restrict__ ys, const double* __restrict__ ts,
+                   double* __restrict__ xo, double* __restrict__ yo, double* __restrict__ to,
+                   double* __restrict__ w_un, const double* __restrict__ s_in,
+                   const double np_recip, double* __restrict__ map, const int32_t nobs,
+                   const FsObs* __restrict__ obs, const int32_t* __restrict__ seen,
+                   const int32_t use_orient, const double dt, const double v, const double om,
+                   const FsPropQ Q, const double* __restrict__ noise, const uint32_t rstep,
+                   const uint64_t seed, double* __restrict__ rec, double* __restrict__ L_out,
+                   double* __restrict__ bmax) {
+    __shared__ double s_d[kFsObsLds], s_phi[kFsObsLds], s_psi[kFsObsLds], s_r0[kFsObsLds],
+        s_r1[kFsObsLds], s_rx[kFsObsLds], s_ry[kFsObsLds], s_vo[kFsObsLds];
+    __shared__ int64_t s_id[kFsObsLds];
+    __shared__ int32_t s_seen[kFsObsLds];
+    __shared__ double s_wmax[kFsThreads / 64];
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    const bool valid = p < n;
+    const int64_t pc = valid ? p : n - 1;
+    // host normals: loaded ahead of the filter.  The device RNG runs after it,
+    // where only the mean, the covariance and L are live (drawn first it costs
+    // a wave per SIMD: DESIGN 11d); its tables are staged here.
+    double xi0 = 0.0, xi1 = 0.0, xi2 = 0.0;
+    RngTabs rtab{};
+    if constexpr (HOSTNOISE) {
+        xi0 = noise[3 * pc];
+        xi1 = noise[3 * pc + 1];
+        xi2 = noise[3 * pc + 2];
+    } else {
+        __shared__ RngTabsLds s_rng;
+        rtab = rng_tabs_stage(&s_rng, (int)threadIdx.x, kFsThreads);
+        __syncthreads();
+    }
+    const double wprev = w_un[pc];
+    // noise-free motion: predict_particle's linear model without its noise
+    double mux, muy, mut;
+    {
+        const double x = xs[pc], y = ys[pc], th = ts[pc];
+        double sn, cs;
+        fast_sincos(th, &sn, &cs);
+        mux = x + v * (dt * cs);
+        muy = y + v * (dt * sn);
+        mut = wrap_angle(th + om * dt);
+    }
+    double c00 = Q.q00, c01 = Q.q01, c02 = Q.q02, c11 = Q.q11, c12 = Q.q12, c22 = Q.q22;
+    double L = 0.0;
+    // ---- pass 1: the proposal
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t cnt = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        SLAM_FS_STAGE_OBS(base, cnt)
+        for (int32_t t = 0; t < cnt; ++t) {
+            if (use_orient) {
+                // scalar update with H = (0, 0, -1)
+                const double e = wrap_angle(s_psi[t] - wrap_angle(kHalfPi - mut));
+                const double so = c22 + s_vo[t];
+                L -= (e * e / so + log(so)) / 2.0;
+                const double k0 = c02 / so, k1 = c12 / so, k2 = c22 / so;
+                const double b0 = c02, b1 = c12, b2 = c22;
+                mux -= k0 * e;
+                muy -= k1 * e;
+                mut -= k2 * e;
+                c00 -= k0 * b0;
+                c01 -= k0 * b1;
+                c02 -= k0 * b2;
+                c11 -= k1 * b1;
+                c12 -= k1 * b2;
+                c22 -= k2 * b2;
+            }
+            if (!s_seen[t]) continue;           // a first sighting carries no pose information
+            const double R0 = s_r0[t], R1 = s_r1[t];
+            const double* m = map + (size_t)kFsComp * (size_t)s_id[t] * (size_t)npad + (size_t)pc;
+            const double mx = m[0], my = m[(size_t)npad];
+            const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                         pyy = m[4 * (size_t)npad];
+            double s, c;
+            sincos(kHalfPi - mut, &s, &c);
+            const double dx = mx - mux, dy = my - muy;
+            const double q = dx * dx + dy * dy, r = sqrt(q);
+            const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+            const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+            const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+            const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+            // A = Sigma H_x^T with H_x = [-H_m | (0, -1)^T]
+            const double a00 = -(c00 * h00 + c01 * h01), a01 = -(c00 * h10 + c01 * h11) - c02;
+            const double a10 = -(c01 * h00 + c11 * h01), a11 = -(c01 * h10 + c11 * h11) - c12;
+            const double a20 = -(c02 * h00 + c12 * h01), a21 = -(c02 * h10 + c12 * h11) - c22;
+            // S = H_m P H_m^T + R + H_x A
+            const double s00 = (h00 * t00 + h01 * t10 + R0) - (h00 * a00 + h01 * a10);
+            const double s01 = (h00 * t01 + h01 * t11) - (h00 * a01 + h01 * a11);
+            const double s11 = (h10 * t01 + h11 * t11 + R1) - (h10 * a01 + h11 * a11 + a21);
+            const double det = s00 * s11 - s01 * s01;
+            const double e0 = s_d[t] - r, e1 = wrap_angle(s_phi[t] - bearing);
+            const double maha = (e0 * e0 * s11 - 2.0 * (e0 * e1) * s01 + e1 * e1 * s00) / det;
+            L -= (maha + log(det)) / 2.0;
+            const double k00 = (a00 * s11 - a01 * s01) / det, k01 = (a01 * s00 - a00 * s01) / det;
+            const double k10 = (a10 * s11 - a11 * s01) / det, k11 = (a11 * s00 - a10 * s01) / det;
+            const double k20 = (a20 * s11 - a21 * s01) / det, k21 = (a21 * s00 - a20 * s01) / det;
+            mux += k00 * e0 + k01 * e1;
+            muy += k10 * e0 + k11 * e1;
+            mut += k20 * e0 + k21 * e1;
+            c00 -= k00 * a00 + k01 * a01;
+            c01 -= k00 * a10 + k01 * a11;
+            c02 -= k00 * a20 + k01 * a21;
+            c11 -= k10 * a10 + k11 * a11;
+            c12 -= k10 * a20 + k11 * a21;
+            c22 -= k20 * a20 + k21 * a21;
+        }
+    }
+    // ---- sample: pose = mean + chol(cov) xi (a non-positive pivot gives NaN)
+    if constexpr (!HOSTNOISE) {
+        double g[6];
+        pair_normals((uint64_t)pc >> 1, rstep, seed, rtab, g);
+        const bool odd = (pc & 1) != 0;
+        xi0 = odd ? g[3] : g[0];
+        xi1 = odd ? g[4] : g[1];
+        xi2 = odd ? g[5] : g[2];
+    }
+    const double l00 = sqrt(c00), l10 = c01 / l00, l20 = c02 / l00;
+    const double l11 = sqrt(c11 - l10 * l10), l21 = (c12 - l20 * l10) / l11;
+    const double l22 = sqrt(c22 - l20 * l20 - l21 * l21);
+    const double x = mux + l00 * xi0;
+    const double y = muy + (l10 * xi0 + l11 * xi1);
+    const double th = mut + (l20 * xi0 + l21 * xi1 + l22 * xi2);
+    if (valid) {
+        xo[p] = x;
+        yo[p] = y;
+        to[p] = th;
+        w_un[p] = norm_w(wprev, *s_in, np_recip);
+        L_out[p] = L;
+        if (rec) {
+            rec[p] = mux;
+            rec[(size_t)npad + p] = muy;
+            rec[2 * (size_t)npad + p] = mut;
+            rec[3 * (size_t)npad + p] = c00;
+            rec[4 * (size_t)npad + p] = c01;
+            rec[5 * (size_t)npad + p] = c02;
+            rec[6 * (size_t)npad + p] = c11;
+            rec[7 * (size_t)npad + p] = c12;
+            rec[8 * (size_t)npad + p] = c22;
+        }
+    }
+    // ---- pass 2: the maps at the sampled pose (fs_update_kernel's expressions)
+    const double psi_p = kHalfPi - th;
+    double s, c;
+    sincos(psi_p, &s, &c);
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t cnt = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        SLAM_FS_STAGE_OBS(base, cnt)
+        for (int32_t t = 0; t < cnt; ++t) {
+            const double R0 = s_r0[t], R1 = s_r1[t];
+            double* m = map + (size_t)kFsComp * (size_t)s_id[t] * (size_t)npad + (size_t)pc;
+            if (!s_seen[t]) {
+                const double rx = s_rx[t], ry = s_ry[t];
+                const double dx = c * rx + s * ry, dy = -s * rx + c * ry;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double a00 = dx / r, a01 = -dy, a10 = dy / r, a11 = dx;
+                if (valid) {
+                    m[0] = x + dx;
+                    m[(size_t)npad] = y + dy;
+                    m[2 * (size_t)npad] = a00 * a00 * R0 + a01 * a01 * R1;
+                    m[3 * (size_t)npad] = a00 * a10 * R0 + a01 * a11 * R1;
+                    m[4 * (size_t)npad] = a10 * a10 * R0 + a11 * a11 * R1;
+                }
+                continue;
+            }
+            const double mx = m[0], my = m[(size_t)npad];
+            const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                         pyy = m[4 * (size_t)npad];
+            const double dx = mx - x, dy = my - y;
+            const double q = dx * dx + dy * dy, r = sqrt(q);
+            const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+            const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+            const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+            const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+            const double s00 = h00 * t00 + h01 * t10 + R0;
+            const double s01 = h00 * t01 + h01 * t11;
+            const double s11 = h10 * t01 + h11 * t11 + R1;
+            const double det = s00 * s11 - s01 * s01;
+            const double e0 = s_d[t] - r, e1 = wrap_angle(s_phi[t] - bearing);
+            const double k00 = (t00 * s11 - t01 * s01) / det, k01 = (t01 * s00 - t00 * s01) / det;
+            const double k10 = (t10 * s11 - t11 * s01) / det, k11 = (t11 * s00 - t10 * s01) / det;
+            const double m00 = k00 * s00 + k01 * s01, m01 = k00 * s01 + k01 * s11;
+            const double m10 = k10 * s00 + k11 * s01, m11 = k10 * s01 + k11 * s11;
+            if (valid) {
+                m[0] = mx + (k00 * e0 + k01 * e1);
+                m[(size_t)npad] = my + (k10 * e0 + k11 * e1);
+                m[2 * (size_t)npad] = pxx - (m00 * k00 + m01 * k01);
+                m[3 * (size_t)npad] = pxy - (m00 * k10 + m01 * k11);
+                m[4 * (size_t)npad] = pyy - (m10 * k10 + m11 * k11);
+            }
+        }
+    }
+    const double wm = fs_wave_max(valid ? L : -INFINITY);
+    if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = wm;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double u = s_wmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) u = fmax(u, s_wmax[w]);
+        bmax[blockIdx.x] = u;
+    }
+}
+#undef SLAM_FS_STAGE_OBS
 
 }  // namespace slam

@@ -1,5 +1,6 @@
 // fs_api.inl -- C-ABI of FastSLAM 1.0, with known data association or with
-// per-particle maximum-likelihood association (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
+// per-particle maximum-likelihood association, and of FastSLAM 2.0's proposal
+// handles (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
 // pf_dist_api.inl is: the poses, weights, exact cumsum, systematic resampling,
 // predict and step end are the single handle's own (a slam_pf with zero
 // landmarks); this file adds the per-particle maps, their update with its log
@@ -43,6 +44,12 @@ struct slam_fs {
     int32_t* assoc_dev = nullptr;          // [assoc_cap][npad] the last update's choices
     int64_t assoc_cap = 0;
     int32_t assoc_k = 0;
+    // FastSLAM 2.0 proposal (slam_fs_create_proposal)
+    bool prop = false;
+    slam_fs_proposal_config pcfg = {};
+    FsPropQ propq = {};                    // Q = F^T F of cfg.pf.q_factor
+    double* prop_rec = nullptr;            // [9][npad] mean and covariance before sampling (record)
+    bool prop_ran = false;                 // a step has filled prop_rec and L
 };
 
 namespace {
@@ -198,6 +205,34 @@ int fs_enqueue_predict(slam_fs* f, const double* control, const double* noise) {
     return SLAM_OK;
 }
 
+// A proposal handle's predict and map update in one launch (fs_proposal_kernel):
+// the noise-free motion, the proposal over the step's k records, the sampled
+// pose and the maps at it.  The counters move as in fs_enqueue_predict; the
+// weights and the step end follow in fs_enqueue_update.
+int fs_enqueue_proposal(slam_fs* f, const double* control, int32_t k, const FsObs* obs,
+                        const double* noise) {
+    slam_pf* h = f->pf;
+    int rc;
+    if ((rc = stage_inputs(h, control, nullptr, noise, std::nan("")))) return rc;
+    const int src = h->cur, dst = 1 - h->cur;
+    fs_tic(f, 1);
+#define SLAM_FS_PROPOSAL(HN)                                                                     \
+    fs_proposal_kernel<HN><<<f->nb, kFsThreads, 0, h->stream>>>(                                 \
+        f->n, f->npad, h->x[src], h->y[src], h->th[src], h->x[dst], h->y[dst], h->th[dst],       \
+        h->w_un, h->s_cur, h->pc.np_recip, f->map[f->mcur], k, obs, f->seen_dev,                 \
+        f->cfg.use_orient, h->pc.dt, control[0], control[1], f->propq, h->noise,                 \
+        (uint32_t)h->stepno, h->cfg.seed, f->prop_rec, f->L, f->bmax)
+    if (noise) SLAM_FS_PROPOSAL(true); else SLAM_FS_PROPOSAL(false);
+#undef SLAM_FS_PROPOSAL
+    fs_toc(f, 1);
+    SLAM_HIP_TRY(hipGetLastError());
+    h->cur = dst;
+    f->prop_ran = true;
+    if ((rc = set_s_one(h))) return rc;
+    h->stepno++;
+    return SLAM_OK;
+}
+
 // the per-particle map update with its log weights, the weights, then the
 // single handle's step end on the current particles (its update stage with
 // zero landmarks: the block partials of the new w_un, then the finalize)
@@ -219,6 +254,12 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
         fs_assoc_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->bcnt, f->nb, f->bmax + f->nb,
                                                              f->cmax_pin_dev);
         fs_weight_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(f->n, f->L, f->bmax + f->nb, h->w_un);
+        SLAM_HIP_TRY(hipGetLastError());
+    } else if (k > 0 && f->prop) {
+        // the proposal launch left L and its block maxima, and updated the maps
+        fs_max_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->nb, f->bmax + f->nb);
+        fs_weight_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(f->n, f->L, f->bmax + f->nb, h->w_un);
+        fs_mark_seen_kernel<<<grid_for(k, kFsThreads), kFsThreads, 0, h->stream>>>(k, obs, f->seen_dev);
         SLAM_HIP_TRY(hipGetLastError());
     } else if (k > 0) {
         const int c = h->cur;
@@ -260,7 +301,9 @@ int fs_step_records(slam_fs* f, const double* control, int32_t k, const FsObs* d
     const int32_t resampling = h->resample_next;
     int rc;
     if (resampling && (rc = fs_enqueue_resample(f, u))) return rc;
-    if ((rc = fs_enqueue_predict(f, control, noise))) return rc;
+    if ((rc = f->prop ? fs_enqueue_proposal(f, control, k, dev_obs, noise)
+                      : fs_enqueue_predict(f, control, noise)))
+        return rc;
     if ((rc = fs_enqueue_update(f, k, dev_obs, resampling))) return rc;
     if (f->assoc) {
         rc = sync_results(h, 0, 1, res);    // the step's one host read, the largest count with it
@@ -324,8 +367,9 @@ int fs_maps_io(slam_fs* f, bool to_device, double* mean, double* cov) {
     return SLAM_OK;
 }
 
-int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, int64_t n_particles,
-                   int32_t n_landmarks, int device, slam_fs** out);
+int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                   const slam_fs_proposal_config* pcfg, int64_t n_particles, int32_t n_landmarks,
+                   int device, slam_fs** out);
 
 }  // namespace
 
@@ -338,7 +382,7 @@ int slam_fs_check_observations(int32_t n_landmarks, int32_t k, const int64_t* id
 
 int slam_fs_create(const slam_fs_config* cfg, int64_t n_particles, int32_t n_landmarks, int device,
                    slam_fs** out) {
-    return fs_create_impl(cfg, nullptr, n_particles, n_landmarks, device, out);
+    return fs_create_impl(cfg, nullptr, nullptr, n_particles, n_landmarks, device, out);
 }
 
 int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
@@ -349,7 +393,18 @@ int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* 
                    "slam_fs_create_assoc: need 1 <= n_particles <= 2^24");
     SLAM_ARG_CHECK(max_landmarks >= 1, "slam_fs_create_assoc: need max_landmarks >= 1");
     SLAM_ARG_CHECK(std::isfinite(acfg->log_p_new), "slam_fs_create_assoc: non-finite log_p_new");
-    return fs_create_impl(cfg, acfg, n_particles, max_landmarks, device, out);
+    return fs_create_impl(cfg, acfg, nullptr, n_particles, max_landmarks, device, out);
+}
+
+int slam_fs_create_proposal(const slam_fs_config* cfg, const slam_fs_proposal_config* pcfg,
+                            int64_t n_particles, int32_t n_landmarks, int device, slam_fs** out) {
+    SLAM_ARG_CHECK(cfg, "slam_fs_create_proposal: NULL cfg");
+    SLAM_ARG_CHECK(pcfg, "slam_fs_create_proposal: NULL pcfg");
+    SLAM_ARG_CHECK(out, "slam_fs_create_proposal: NULL out");
+    *out = nullptr;
+    SLAM_ARG_CHECK(cfg->pf.motion == SLAM_MOTION_LINEAR,
+                   "slam_fs_create_proposal: pf.motion must be SLAM_MOTION_LINEAR");
+    return fs_create_impl(cfg, nullptr, pcfg, n_particles, n_landmarks, device, out);
 }
 
 }  // extern "C"
@@ -357,7 +412,8 @@ int slam_fs_create_assoc(const slam_fs_config* cfg, const slam_fs_assoc_config* 
 namespace {
 
 // the device side of fs_create_impl
-int fs_create_buffers(slam_fs* f, const slam_fs_assoc_config* acfg) {
+int fs_create_buffers(slam_fs* f, const slam_fs_assoc_config* acfg,
+                      const slam_fs_proposal_config* pcfg) {
     DeviceMem& m = f->mem;
     const hipStream_t st = f->pf->stream;
     const size_t nl = (size_t)f->nl, npad = (size_t)f->npad;
@@ -387,6 +443,14 @@ int fs_create_buffers(slam_fs* f, const slam_fs_assoc_config* acfg) {
             return rc;
         *f->cmax_pin = 0;
     }
+    if (pcfg) {
+        f->prop = true;
+        f->pcfg.record = pcfg->record ? 1 : 0;
+        const double* F = f->cfg.pf.q_factor;
+        auto q = [F](int i, int j) { return (F[i] * F[j] + F[3 + i] * F[3 + j]) + F[6 + i] * F[6 + j]; };
+        f->propq = FsPropQ{q(0, 0), q(0, 1), q(0, 2), q(1, 1), q(1, 2), q(2, 2)};
+        if (f->pcfg.record && (rc = m.alloc(&f->prop_rec, 9 * npad))) return rc;
+    }
     for (auto& pr : f->ev)
         for (auto& ev : pr)
             if ((rc = m.event(&ev))) return rc;
@@ -395,8 +459,9 @@ int fs_create_buffers(slam_fs* f, const slam_fs_assoc_config* acfg) {
 }
 
 // slam_fs_create, and slam_fs_create_assoc's second half (acfg != NULL)
-int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, int64_t n_particles,
-                   int32_t n_landmarks, int device, slam_fs** out) {
+int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                   const slam_fs_proposal_config* pcfg, int64_t n_particles, int32_t n_landmarks,
+                   int device, slam_fs** out) {
     SLAM_ARG_CHECK(cfg && out, "slam_fs_create: NULL argument");
     *out = nullptr;
     SLAM_ARG_CHECK(n_particles >= 1 && n_particles <= (int64_t(1) << 24),
@@ -423,7 +488,7 @@ int fs_create_impl(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg, 
     f->nl = n_landmarks;
     f->nb = (int32_t)(f->npad / kFsThreads);
     f->seen.assign((size_t)n_landmarks, 0);
-    if ((rc = fs_create_buffers(f, acfg)))
+    if ((rc = fs_create_buffers(f, acfg, pcfg)))
         return fail(rc, std::string("slam_fs_create: ") + slam_last_error());
     *out = fp.release();
     return SLAM_OK;
@@ -582,6 +647,7 @@ int slam_fs_resample(slam_fs* f, double u_resample, int32_t force, int32_t* resa
 
 int slam_fs_predict(slam_fs* f, const double* control, const double* noise) {
     SLAM_ARG_CHECK(f && control, "slam_fs_predict: NULL argument");
+    SLAM_ARG_CHECK(!f->prop, "slam_fs_predict: a proposal handle needs the step's scan (slam_fs_step)");
     slam_pf* h = f->pf;
     h->prep_step = -1;
     SLAM_HIP_TRY(hipSetDevice(h->device));
@@ -594,6 +660,7 @@ int slam_fs_predict(slam_fs* f, const double* control, const double* noise) {
 int slam_fs_update(slam_fs* f, int32_t k, const int64_t* ids, const double* obs,
                    slam_pf_result* res) {
     SLAM_ARG_CHECK(f, "slam_fs_update: NULL handle");
+    SLAM_ARG_CHECK(!f->prop, "slam_fs_update: a proposal handle needs the step's control (slam_fs_step)");
     int rc = fs_check_obs(f, "slam_fs_update", k, ids, obs);
     if (rc) return rc;
     slam_pf* h = f->pf;
@@ -692,6 +759,29 @@ int slam_fs_get_assoc(slam_fs* f, int32_t* out) {
                                   sizeof(int32_t) * (size_t)f->npad, sizeof(int32_t) * (size_t)f->n,
                                   (size_t)f->assoc_k, hipMemcpyDeviceToHost, f->pf->stream));
     SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    return SLAM_OK;
+}
+
+int slam_fs_get_proposal(slam_fs* f, double* mean, double* cov, double* L) {
+    SLAM_ARG_CHECK(f, "slam_fs_get_proposal: NULL handle");
+    SLAM_ARG_CHECK(f->prop, "slam_fs_get_proposal: not a proposal handle");
+    SLAM_ARG_CHECK(f->pcfg.record, "slam_fs_get_proposal: the handle does not record (record = 0)");
+    SLAM_ARG_CHECK(f->prop_ran, "slam_fs_get_proposal: no step has run yet");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    const hipStream_t st = f->pf->stream;
+    const size_t n = (size_t)f->n, npad = (size_t)f->npad;
+    std::vector<double> rec;
+    if (mean || cov) {
+        rec.resize(9 * npad);
+        SLAM_HIP_TRY(hipMemcpyAsync(rec.data(), f->prop_rec, sizeof(double) * 9 * npad,
+                                    hipMemcpyDeviceToHost, st));
+    }
+    if (L) SLAM_HIP_TRY(hipMemcpyAsync(L, f->L, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    SLAM_HIP_TRY(hipStreamSynchronize(st));
+    for (size_t p = 0; p < n && (mean || cov); ++p) {
+        for (int c = 0; c < 3 && mean; ++c) mean[3 * p + c] = rec[(size_t)c * npad + p];
+        for (int c = 0; c < 6 && cov; ++c) cov[6 * p + c] = rec[(size_t)(3 + c) * npad + p];
+    }
     return SLAM_OK;
 }
 

@@ -61,7 +61,13 @@ class FastSLAM:
     noise=(r_dist, r_dir, r_orient), use_orient, ess_threshold, seed, device);
     the measurement noise defaults to ScanSensor's (10 %, 3 deg, 3 deg).
     ``association="ml"``: ``n_landmarks`` is the capacity of a particle's map and
-    the observations' ids are dropped (also ``p_new``, ``record_assoc``)."""
+    the observations' ids are dropped (also ``p_new``, ``record_assoc``).
+    ``proposal="measurement"`` (FastSLAM 2.0; known association, linear
+    motion): every particle filters its pose through the step's scan and draws
+    it from the resulting N(mu, Sigma).  ``step``'s ``noise`` then means three
+    standard normals per particle ([NP][3], pose = mu + chol(Sigma) noise), not
+    the Q-shaped motion noise of the default proposal; ``record_proposal``
+    keeps mu, Sigma and the log weights for ``dev.last_proposal()``."""
 
     def __init__(self, n_particles, n_landmarks, **kw):
         self.dev = DeviceFastSLAM(n_particles, n_landmarks, **kw)

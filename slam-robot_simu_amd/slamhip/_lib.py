@@ -75,6 +75,13 @@ class FSAssocConfig(C.Structure):
 FS_ASSOC_MAX_OBS = 4096     # SLAM_FS_ASSOC_MAX_OBS
 
 
+class FSProposalConfig(C.Structure):
+    _fields_ = [("record", C.c_int32), ("pad0", C.c_int32)]
+
+
+FS_PROPOSAL = ("motion", "measurement")     # DeviceFastSLAM(proposal=...)
+
+
 class GraphEdge(C.Structure):
     _fields_ = [("time_bfr", C.c_int64), ("pose_bfr", C.c_int64), ("time_aft", C.c_int64),
                 ("pose_aft", C.c_int64), ("obs_bfr", C.c_double * 3), ("obs_aft", C.c_double * 3)]
@@ -223,6 +230,9 @@ SIGNATURES = {
     "slam_fs_set_counts": (C.c_int, [_P, _I32]),
     "slam_fs_get_counts": (C.c_int, [_P, _I32]),
     "slam_fs_get_assoc": (C.c_int, [_P, _I32]),
+    "slam_fs_create_proposal": (C.c_int, [C.POINTER(FSConfig), C.POINTER(FSProposalConfig), C.c_int64,
+                                          C.c_int32, C.c_int, C.POINTER(_P)]),
+    "slam_fs_get_proposal": (C.c_int, [_P, _D, _D, _D]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

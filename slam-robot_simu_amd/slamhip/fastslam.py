@@ -1,5 +1,6 @@
 """Device FastSLAM 1.0 (known data association, or per-particle
-maximum-likelihood association): a handle on libslam_hip's slam_fs_* entry
+maximum-likelihood association) and 2.0 (known association, poses drawn from
+the observation-informed proposal): a handle on libslam_hip's slam_fs_* entry
 points.
 
 Every particle carries a pose, a weight and one 2-D EKF (mean, symmetric 2 x 2
@@ -14,6 +15,12 @@ With ``association="ml"`` the observations carry no ids: every particle scores
 an observation against the landmarks of its own map, takes the likeliest (or
 starts a new landmark when none reaches ``p_new``), and ``n_landmarks`` is the
 capacity of every particle's map (include/slam_hip.h states the contract).
+
+With ``proposal="measurement"`` (FastSLAM 2.0; known association and linear
+motion) a step filters every particle's pose through the scan before drawing
+it: the pose comes from N(mu, Sigma) with the scan's seen landmarks folded in,
+and the weight no longer depends on the draw.  ``noise`` is then three
+standard normals per particle, not Q-shaped noise.
 """
 from __future__ import annotations
 
@@ -22,7 +29,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FSAssocConfig, FSConfig, PFResult, check, dptr
+from ._lib import FSAssocConfig, FSConfig, FSProposalConfig, PFResult, check, dptr
 from .pf import DeviceParticleFilter, RunResults, _f64, make_config
 
 
@@ -53,8 +60,13 @@ class DeviceFastSLAM:
     every observation) or "ml" (per-particle maximum likelihood: ``ids`` is
     None everywhere, ``n_landmarks`` is the capacity of a particle's map,
     ``p_new`` the likelihood below which an observation starts a new landmark,
-    ``record_assoc`` keeps each update's choices for ``last_assoc``).  The
-    other keywords are DeviceParticleFilter's."""
+    ``record_assoc`` keeps each update's choices for ``last_assoc``).
+    ``proposal``: "motion" (FastSLAM 1.0: the pose from the motion model) or
+    "measurement" (FastSLAM 2.0: the pose from the proposal that has seen the
+    scan; ``step``'s ``noise`` is then [NP][3] standard normals, ``predict`` and
+    ``update`` raise, ``record_proposal`` keeps each step's mean, covariance
+    and log weight for ``last_proposal``).  The other keywords are
+    DeviceParticleFilter's."""
 
     ESS_CONFIRM_BAND = DeviceParticleFilter.ESS_CONFIRM_BAND
 
@@ -62,9 +74,14 @@ class DeviceFastSLAM:
                  x0=(10.0, 0.0, np.pi / 2), motion="linear",
                  noise=(0.1, np.deg2rad(3.0), np.deg2rad(3.0)), use_orient=True,
                  ess_threshold=None, seed=0, device=0, association="known",
-                 p_new=P_NEW_DEFAULT, record_assoc=False):
+                 p_new=P_NEW_DEFAULT, record_assoc=False, proposal="motion",
+                 record_proposal=False):
         if association not in ("known", "ml"):
             raise ValueError("association: 'known' or 'ml'")
+        if proposal not in _lib.FS_PROPOSAL:
+            raise ValueError("proposal: 'motion' or 'measurement'")
+        if proposal == "measurement" and association == "ml":
+            raise ValueError("proposal='measurement' needs association='known'")
         lib = _lib.load()
         self.n = int(n_particles)
         self.nl = int(n_landmarks)
@@ -77,6 +94,8 @@ class DeviceFastSLAM:
         self.motion = motion
         self.association = association
         self.record_assoc = bool(record_assoc)
+        self.proposal = proposal
+        self.record_proposal = bool(record_proposal)
         self._last_k = 0
         h = C.c_void_p()
         if association == "ml":
@@ -86,6 +105,10 @@ class DeviceFastSLAM:
             self.acfg = acfg
             check(lib.slam_fs_create_assoc(C.byref(cfg), C.byref(acfg), self.n, self.nl, int(device),
                                            C.byref(h)), "slam_fs_create_assoc")
+        elif proposal == "measurement":
+            pcfg = FSProposalConfig(int(self.record_proposal), 0)
+            check(lib.slam_fs_create_proposal(C.byref(cfg), C.byref(pcfg), self.n, self.nl,
+                                              int(device), C.byref(h)), "slam_fs_create_proposal")
         else:
             check(lib.slam_fs_create(C.byref(cfg), self.n, self.nl, int(device), C.byref(h)),
                   "slam_fs_create")
@@ -187,6 +210,15 @@ class DeviceFastSLAM:
               "slam_fs_get_assoc")
         return a
 
+    def last_proposal(self):
+        """proposal="measurement", record_proposal=True: the last step's
+        proposal before sampling -- mean [NP][3], covariance [NP][6] (00 01 02
+        11 12 22) and log weight L [NP]."""
+        mean, cov, L = np.empty((self.n, 3)), np.empty((self.n, 6)), np.empty(self.n)
+        check(self._lib.slam_fs_get_proposal(self._h, dptr(mean), dptr(cov), dptr(L)),
+              "slam_fs_get_proposal")
+        return mean, cov, L
+
     def best_map(self):
         """The map estimate: the map of the last step's heaviest particle, as
         x_est is its pose."""
@@ -282,7 +314,9 @@ class DeviceFastSLAM:
 
     def timing(self):
         """HIP-event ms of the last step's {map gather, predict, map update +
-        weights, step end}."""
+        weights, step end}; with proposal="measurement" one launch does the
+        motion, the proposal, the sampling and the map update ("predict"), and
+        "map_update" is the weights alone."""
         out = np.zeros(4)
         check(self._lib.slam_fs_timing(self._h, dptr(out)), "slam_fs_timing")
         return dict(zip(("map_gather", "predict", "map_update", "step_end"), out.tolist()))
