@@ -655,6 +655,66 @@ int slam_fs_create_proposal(const slam_fs_config* cfg, const slam_fs_proposal_co
  * stepped. */
 int slam_fs_get_proposal(slam_fs* h, double* mean, double* cov, double* L);
 
+/* --------------------------------------------------------------------
+ * FastSLAM 2.0 without ids: data association under the proposal.  The handle
+ * is an associating handle (particle p holds cnt_p <= cap landmarks in slots
+ * 0..cnt_p-1) and a proposal handle (Q = F^T F, SLAM_MOTION_LINEAR) at once;
+ * the association score marginalises the pose uncertainty of the proposal.
+ *
+ * One step:
+ *   1. resample: exactly as on an associating handle (poses, counts, and the
+ *      map rows below the source's count);
+ *   2. proposal with association, per particle: mu = the noise-free linear
+ *      motion, Sigma = Q, L = 0, cnt0_p = the count at the start, c = cnt0_p;
+ *      then for each observation (d, phi, psi) in the order given:
+ *      a. the orientation step of the proposal handle (use_orient), unchanged:
+ *         s_o, L -= (e^2 / s_o + ln s_o) / 2, the scalar update of mu, Sigma;
+ *      b. the candidates are the slots j < cnt0_p that no earlier observation of
+ *         this step has matched in this particle (a slot created in this step is
+ *         never a candidate);
+ *      c. l_j = -(e^T S^-1 e + ln det S) / 2 - ln(2 pi) with e and S of the
+ *         proposal handle's seen-landmark step, linearised at the current mu and
+ *         the slot's prior (m_j, P_j): A = Sigma H_x^T,
+ *         S = H_m P_j H_m^T + R + H_x A -- the associating handle's score with
+ *         the pose covariance folded into S (equal to it where Sigma = 0);
+ *      d. best = the largest l_j; the comparison is strict, so the lowest slot
+ *         wins a tie and a NaN never wins;
+ *      e. no candidate, or l_best < log_p_new: L += log_p_new, mu and Sigma do
+ *         not change (a first sighting carries no pose information); the choice
+ *         is -1 and c += 1 if c < cap, otherwise the choice is -2.  Otherwise
+ *         L += l_best, the Kalman update of mu and Sigma with slot best
+ *         (K = A S^-1 through the adjugate), the slot is marked matched, and the
+ *         choice is best;
+ *   3. sample: step 3 of the proposal handle, unchanged (noise non-NULL: three
+ *      STANDARD normals per particle);
+ *   4. maps at the sampled pose, per observation in order and by the recorded
+ *      choice: a slot >= 0 takes the EKF update of that slot without the weight
+ *      term, -1 the first-sighting mean and covariance in slot cnt_p and then
+ *      cnt_p += 1, -2 nothing.  Step 2 reads every prior before any slot is
+ *      rewritten;
+ *   5. w_un = w exp(L - max_p L) and the step end, unchanged.
+ * With k = 0 a step is mu + chol(Q) xi, with weights and counts kept.  The
+ * copies of a resampled particle share mu, Sigma, L, map and choices, so they
+ * carry bit-equal weights and max_idx is the first of equals.
+ *
+ * ids must be NULL and 0 <= k <= SLAM_FS_ASSOC_MAX_OBS.  slam_fs_predict and
+ * slam_fs_update return SLAM_ERR_ARG as on a proposal handle.
+ * slam_fs_set_counts / get_counts, the map accessors, slam_fs_info,
+ * slam_fs_resample and slam_fs_load_observations / slam_fs_run behave as on an
+ * associating handle; slam_fs_timing's phases mean what they mean on a proposal
+ * handle.  slam_fs_get_proposal works when pcfg->record is set.
+ * slam_fs_get_assoc works after any step with k > 0 whatever acfg->record says:
+ * the choices stay in memory between the kernel's passes (4 B x k x
+ * n_particles; SLAM_ERR_HIP from the step if that does not fit).
+ *
+ * SLAM_ERR_ARG before any HIP call for a NULL cfg, acfg, pcfg or out, a
+ * non-finite log_p_new, max_landmarks < 1, cfg->pf.motion !=
+ * SLAM_MOTION_LINEAR, and slam_fs_create's own cases.
+ * -------------------------------------------------------------------- */
+int slam_fs_create_assoc_proposal(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                                  const slam_fs_proposal_config* pcfg, int64_t n_particles,
+                                  int32_t max_landmarks, int device, slam_fs** out);
+
 /* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve
  * (graph_based_slam.py: setPairObs :362-439, updateEstPose :452-514) and

@@ -1,8 +1,9 @@
 // fastslam.inl -- gfx950 kernels of FastSLAM 1.0 with known data association
 // (included by fs_api.inl): the per-particle landmark EKFs with their log
 // weights, the weight pass, and the resampling gather of whole maps; below
-// them the kernels of per-particle maximum-likelihood association, and last
-// the one kernel of FastSLAM 2.0's observation-informed proposal.
+// them the kernels of per-particle maximum-likelihood association, the one
+// kernel of FastSLAM 2.0's observation-informed proposal, and last that
+// proposal with the association inside it.
 //
 // Map layout: component-major per landmark,
 //     map[(5 j + c) * npad + p],   c = mx, my, pxx, pxy, pyy
@@ -714,5 +715,317 @@ fs_proposal_kernel(const int64_t n, const int64_t npad, const double* __restrict
     }
 }
 #undef SLAM_FS_STAGE_OBS
+
+// ------------------------------------------------------------------------
+// FastSLAM 2.0 with per-particle maximum-likelihood association:
+// the scan of fs_assoc_update_kernel with fs_proposal_kernel's three-state
+// filter inside it.  No ids, linear motion.
+// ------------------------------------------------------------------------
+// The block's next kFsObsLds observations into LDS, without ids
+#define SLAM_FS_STAGE_SCAN(base, cnt)                                                            \
+    __syncthreads();                                                                             \
+    if ((int32_t)threadIdx.x < (cnt)) {                                                          \
+        const FsObs o = obs[(base) + threadIdx.x];                                               \
+        s_d[threadIdx.x] = o.d;                                                                  \
+        s_phi[threadIdx.x] = o.phi;                                                              \
+        s_psi[threadIdx.x] = o.psi;                                                              \
+        s_r0[threadIdx.x] = o.r0;                                                                \
+        s_r1[threadIdx.x] = o.r1;                                                                \
+        s_rx[threadIdx.x] = o.rx;                                                                \
+        s_ry[threadIdx.x] = o.ry;                                                                \
+        s_vo[threadIdx.x] = o.vo;                                                                \
+    }                                                                                            \
+    __syncthreads();
+
+// One lane per particle, one launch, two passes over the step's observations.
+// Pass 1 is fs_proposal_kernel's filter on the pose with the association
+// inside it: per observation the wave walks the slots below its largest count
+// (every lane loads the same row and stamp; lanes past their own count or on a
+// slot already matched in this call are masked), each candidate scored at the
+// current mean with the pose covariance folded into S.  Only the best score
+// and slot are kept: the chosen slot is re-read and its A, S and e recomputed
+// for the Kalman update of the pose.  The choice (slot, -1 new, -2 dropped)
+// goes to assoc[t][npad]; the maps are only read.  Then the draw, as
+// fs_proposal_kernel's, and pass 2: the lane's own choices read back, and the
+// map update of fs_update_kernel at the sampled pose (a new landmark in slot
+// cnt).  Padding lanes have no candidates and store nothing.
+// Three waves per SIMD (166 / 167 VGPRs, no scratch), as its parents.
+template <bool HOSTNOISE>
+__global__ __launch_bounds__(kFsThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void
+fs_assoc_proposal_kernel(
+    const int64_t n, const int64_t npad, const double* __restrict__ xs,
+    const double* __restrict__ ys, const double* __restrict__ ts, double* __restrict__ xo,
+    double* __restrict__ yo, double* __restrict__ to, double* __restrict__ w_un,
+    const double* __restrict__ s_in, const double np_recip, double* __restrict__ map,
+    int32_t* __restrict__ cnt_io, int32_t* __restrict__ stamp, const int32_t call,
+    const int32_t cap, const int32_t nobs, const FsObs* __restrict__ obs, const int32_t use_orient,
+    const double dt, const double v, const double om, const FsPropQ Q, const double log_p_new,
+    const double* __restrict__ noise, const uint32_t rstep, const uint64_t seed,
+    int32_t* assoc, double* __restrict__ rec, double* __restrict__ L_out,
+    double* __restrict__ bmax, int32_t* __restrict__ bcnt) {
+    __shared__ double s_d[kFsObsLds], s_phi[kFsObsLds], s_psi[kFsObsLds], s_r0[kFsObsLds],
+        s_r1[kFsObsLds], s_rx[kFsObsLds], s_ry[kFsObsLds], s_vo[kFsObsLds];
+    __shared__ double s_wmax[kFsThreads / 64];
+    __shared__ int32_t s_cmax[kFsThreads / 64];
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
+    const bool valid = p < n;
+    const int64_t pc = valid ? p : n - 1;
+    // the device RNG runs after pass 1; its tables are staged here
+    RngTabs rtab{};
+    if constexpr (!HOSTNOISE) {
+        __shared__ RngTabsLds s_rng;
+        rtab = rng_tabs_stage(&s_rng, (int)threadIdx.x, kFsThreads);
+        __syncthreads();
+    }
+    // noise-free motion: predict_particle's linear model without its noise
+    double mux, muy, mut;
+    {
+        const double x = xs[pc], y = ys[pc], th = ts[pc];
+        double sn, cs;
+        fast_sincos(th, &sn, &cs);
+        mux = x + v * (dt * cs);
+        muy = y + v * (dt * sn);
+        mut = wrap_angle(th + om * dt);
+    }
+    double c00 = Q.q00, c01 = Q.q01, c02 = Q.q02, c11 = Q.q11, c12 = Q.q12, c22 = Q.q22;
+    const int32_t cnt0 = valid ? cnt_io[p] : 0;     // padding lanes: no candidates, no stores
+    // the wave's largest count, bit by bit through ballots: a scalar, and no
+    // shuffle addresses stay live across pass 1 for the reductions at the end
+    // (which costs the third wave per SIMD: DESIGN 11e)
+    int32_t jmax = 0;
+#pragma unroll
+    for (int b = 30; b >= 0; --b) {
+        const int32_t probe = jmax | (int32_t(1) << b);
+        if (__ballot(cnt0 >= probe) != 0) jmax = probe;
+    }
+    int32_t cnew = cnt0;                            // the count after this step
+    double L = 0.0;
+    // ---- pass 1: the proposal with the association
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t m_obs = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        SLAM_FS_STAGE_SCAN(base, m_obs)
+#pragma unroll 1
+        for (int32_t t = 0; t < m_obs; ++t) {
+            if (use_orient) {
+                // scalar update with H = (0, 0, -1)
+                const double e = wrap_angle(s_psi[t] - wrap_angle(kHalfPi - mut));
+                const double so = c22 + s_vo[t];
+                L -= (e * e / so + log(so)) / 2.0;
+                const double k0 = c02 / so, k1 = c12 / so, k2 = c22 / so;
+                const double b0 = c02, b1 = c12, b2 = c22;
+                mux -= k0 * e;
+                muy -= k1 * e;
+                mut -= k2 * e;
+                c00 -= k0 * b0;
+                c01 -= k0 * b1;
+                c02 -= k0 * b2;
+                c11 -= k1 * b1;
+                c12 -= k1 * b2;
+                c22 -= k2 * b2;
+            }
+            double s, c;
+            sincos(kHalfPi - mut, &s, &c);
+            double best = -INFINITY;
+            int32_t bj = -1;
+            {
+                const double R0 = s_r0[t], R1 = s_r1[t], zd = s_d[t], zphi = s_phi[t];
+#pragma unroll 1
+                for (int32_t j = 0; j < jmax; ++j) {
+                    const size_t row = (size_t)kFsComp * (size_t)j * (size_t)npad + (size_t)pc;
+                    const int32_t st = stamp[(size_t)j * (size_t)npad + (size_t)pc];
+                    const double mx = map[row], my = map[row + (size_t)npad];
+                    const double pxx = map[row + 2 * (size_t)npad],
+                                 pxy = map[row + 3 * (size_t)npad],
+                                 pyy = map[row + 4 * (size_t)npad];
+                    const double dx = mx - mux, dy = my - muy;
+                    const double q = dx * dx + dy * dy, r = sqrt(q);
+                    const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+                    const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+                    const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+                    const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+                    const double a00 = -(c00 * h00 + c01 * h01),
+                                 a01 = -(c00 * h10 + c01 * h11) - c02;
+                    const double a10 = -(c01 * h00 + c11 * h01),
+                                 a11 = -(c01 * h10 + c11 * h11) - c12;
+                    const double a21 = -(c02 * h10 + c12 * h11) - c22;
+                    const double s00 = (h00 * t00 + h01 * t10 + R0) - (h00 * a00 + h01 * a10);
+                    const double s01 = (h00 * t01 + h01 * t11) - (h00 * a01 + h01 * a11);
+                    const double s11 = (h10 * t01 + h11 * t11 + R1) - (h10 * a01 + h11 * a11 + a21);
+                    const double det = s00 * s11 - s01 * s01;
+                    const double e0 = zd - r, e1 = wrap_angle(zphi - bearing);
+                    const double maha =
+                        (e0 * e0 * s11 - 2.0 * (e0 * e1) * s01 + e1 * e1 * s00) / det;
+                    const double l = -(maha + log(det)) / 2.0 - kFsLn2Pi;
+                    // strictly greater: a tie keeps the lowest slot; NaN never wins
+                    if (j < cnt0 && st != call && l > best) {
+                        best = l;
+                        bj = j;
+                    }
+                }
+            }
+            int32_t a;
+            if (bj < 0 || best < log_p_new) {
+                // a first sighting carries no pose information
+                L += log_p_new;
+                a = -2;
+                if (cnew < cap) {
+                    a = -1;
+                    ++cnew;
+                }
+            } else {
+                const double R0 = s_r0[t], R1 = s_r1[t];
+                const double* m = map + (size_t)kFsComp * (size_t)bj * (size_t)npad + (size_t)pc;
+                const double mx = m[0], my = m[(size_t)npad];
+                const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                             pyy = m[4 * (size_t)npad];
+                const double dx = mx - mux, dy = my - muy;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+                const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+                const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+                const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+                // A = Sigma H_x^T with H_x = [-H_m | (0, -1)^T]
+                const double a00 = -(c00 * h00 + c01 * h01), a01 = -(c00 * h10 + c01 * h11) - c02;
+                const double a10 = -(c01 * h00 + c11 * h01), a11 = -(c01 * h10 + c11 * h11) - c12;
+                const double a20 = -(c02 * h00 + c12 * h01), a21 = -(c02 * h10 + c12 * h11) - c22;
+                // S = H_m P H_m^T + R + H_x A
+                const double s00 = (h00 * t00 + h01 * t10 + R0) - (h00 * a00 + h01 * a10);
+                const double s01 = (h00 * t01 + h01 * t11) - (h00 * a01 + h01 * a11);
+                const double s11 = (h10 * t01 + h11 * t11 + R1) - (h10 * a01 + h11 * a11 + a21);
+                const double det = s00 * s11 - s01 * s01;
+                const double e0 = s_d[t] - r, e1 = wrap_angle(s_phi[t] - bearing);
+                L += best;
+                const double k00 = (a00 * s11 - a01 * s01) / det, k01 = (a01 * s00 - a00 * s01) / det;
+                const double k10 = (a10 * s11 - a11 * s01) / det, k11 = (a11 * s00 - a10 * s01) / det;
+                const double k20 = (a20 * s11 - a21 * s01) / det, k21 = (a21 * s00 - a20 * s01) / det;
+                mux += k00 * e0 + k01 * e1;
+                muy += k10 * e0 + k11 * e1;
+                mut += k20 * e0 + k21 * e1;
+                c00 -= k00 * a00 + k01 * a01;
+                c01 -= k00 * a10 + k01 * a11;
+                c02 -= k00 * a20 + k01 * a21;
+                c11 -= k10 * a10 + k11 * a11;
+                c12 -= k10 * a20 + k11 * a21;
+                c22 -= k20 * a20 + k21 * a21;
+                // bj >= 0 implies a valid lane (padding lanes have no candidates)
+                stamp[(size_t)bj * (size_t)npad + (size_t)pc] = call;
+                a = bj;
+            }
+            if (valid) assoc[(size_t)(base + t) * (size_t)npad + (size_t)p] = a;
+        }
+    }
+    // ---- sample: pose = mean + chol(cov) xi (a non-positive pivot gives NaN)
+    double xi0, xi1, xi2;
+    if constexpr (HOSTNOISE) {
+        xi0 = noise[3 * pc];
+        xi1 = noise[3 * pc + 1];
+        xi2 = noise[3 * pc + 2];
+    } else {
+        double g[6];
+        pair_normals((uint64_t)pc >> 1, rstep, seed, rtab, g);
+        const bool odd = (pc & 1) != 0;
+        xi0 = odd ? g[3] : g[0];
+        xi1 = odd ? g[4] : g[1];
+        xi2 = odd ? g[5] : g[2];
+    }
+    const double l00 = sqrt(c00), l10 = c01 / l00, l20 = c02 / l00;
+    const double l11 = sqrt(c11 - l10 * l10), l21 = (c12 - l20 * l10) / l11;
+    const double l22 = sqrt(c22 - l20 * l20 - l21 * l21);
+    const double x = mux + l00 * xi0;
+    const double y = muy + (l10 * xi0 + l11 * xi1);
+    const double th = mut + (l20 * xi0 + l21 * xi1 + l22 * xi2);
+    if (valid) {
+        xo[p] = x;
+        yo[p] = y;
+        to[p] = th;
+        w_un[p] = norm_w(w_un[p], *s_in, np_recip);
+        L_out[p] = L;
+        cnt_io[p] = cnew;
+        if (rec) {
+            rec[p] = mux;
+            rec[(size_t)npad + p] = muy;
+            rec[2 * (size_t)npad + p] = mut;
+            rec[3 * (size_t)npad + p] = c00;
+            rec[4 * (size_t)npad + p] = c01;
+            rec[5 * (size_t)npad + p] = c02;
+            rec[6 * (size_t)npad + p] = c11;
+            rec[7 * (size_t)npad + p] = c12;
+            rec[8 * (size_t)npad + p] = c22;
+        }
+    }
+    // ---- pass 2: the maps at the sampled pose, by the recorded choices
+    // (fs_update_kernel's expressions).  Pass 1 read every prior it needed.
+    const double psi_p = kHalfPi - th;
+    double s, c;
+    sincos(psi_p, &s, &c);
+    int32_t cnt = cnt0;
+    for (int32_t base = 0; base < nobs; base += kFsObsLds) {
+        const int32_t m_obs = nobs - base < kFsObsLds ? nobs - base : kFsObsLds;
+        SLAM_FS_STAGE_SCAN(base, m_obs)
+#pragma unroll 1
+        for (int32_t t = 0; t < m_obs; ++t) {
+            // the lane's own store of pass 1; padding lanes do nothing
+            const int32_t a = valid ? assoc[(size_t)(base + t) * (size_t)npad + (size_t)p] : -2;
+            const double R0 = s_r0[t], R1 = s_r1[t];
+            if (a == -1) {
+                double* m = map + (size_t)kFsComp * (size_t)cnt * (size_t)npad + (size_t)pc;
+                const double rx = s_rx[t], ry = s_ry[t];
+                const double dx = c * rx + s * ry, dy = -s * rx + c * ry;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double a00 = dx / r, a01 = -dy, a10 = dy / r, a11 = dx;
+                m[0] = x + dx;
+                m[(size_t)npad] = y + dy;
+                m[2 * (size_t)npad] = a00 * a00 * R0 + a01 * a01 * R1;
+                m[3 * (size_t)npad] = a00 * a10 * R0 + a01 * a11 * R1;
+                m[4 * (size_t)npad] = a10 * a10 * R0 + a11 * a11 * R1;
+                ++cnt;
+            } else if (a >= 0) {
+                double* m = map + (size_t)kFsComp * (size_t)a * (size_t)npad + (size_t)pc;
+                const double mx = m[0], my = m[(size_t)npad];
+                const double pxx = m[2 * (size_t)npad], pxy = m[3 * (size_t)npad],
+                             pyy = m[4 * (size_t)npad];
+                const double dx = mx - x, dy = my - y;
+                const double q = dx * dx + dy * dy, r = sqrt(q);
+                const double bearing = atan2(s * dx + c * dy, c * dx - s * dy);
+                const double h00 = dx / r, h01 = dy / r, h10 = -dy / q, h11 = dx / q;
+                const double t00 = pxx * h00 + pxy * h01, t01 = pxx * h10 + pxy * h11;
+                const double t10 = pxy * h00 + pyy * h01, t11 = pxy * h10 + pyy * h11;
+                const double s00 = h00 * t00 + h01 * t10 + R0;
+                const double s01 = h00 * t01 + h01 * t11;
+                const double s11 = h10 * t01 + h11 * t11 + R1;
+                const double det = s00 * s11 - s01 * s01;
+                const double e0 = s_d[t] - r, e1 = wrap_angle(s_phi[t] - bearing);
+                const double k00 = (t00 * s11 - t01 * s01) / det, k01 = (t01 * s00 - t00 * s01) / det;
+                const double k10 = (t10 * s11 - t11 * s01) / det, k11 = (t11 * s00 - t10 * s01) / det;
+                const double m00 = k00 * s00 + k01 * s01, m01 = k00 * s01 + k01 * s11;
+                const double m10 = k10 * s00 + k11 * s01, m11 = k10 * s01 + k11 * s11;
+                m[0] = mx + (k00 * e0 + k01 * e1);
+                m[(size_t)npad] = my + (k10 * e0 + k11 * e1);
+                m[2 * (size_t)npad] = pxx - (m00 * k00 + m01 * k01);
+                m[3 * (size_t)npad] = pxy - (m00 * k10 + m01 * k11);
+                m[4 * (size_t)npad] = pyy - (m10 * k10 + m11 * k11);
+            }
+        }
+    }
+    const double wm = fs_wave_max(valid ? L : -INFINITY);
+    const int32_t cm = fs_wave_max_i32(valid ? cnew : 0);
+    if ((threadIdx.x & 63) == 0) {
+        s_wmax[threadIdx.x >> 6] = wm;
+        s_cmax[threadIdx.x >> 6] = cm;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double u = s_wmax[0];
+        int32_t k = s_cmax[0];
+#pragma unroll
+        for (int w = 1; w < kFsThreads / 64; ++w) {
+            u = fmax(u, s_wmax[w]);
+            k = s_cmax[w] > k ? s_cmax[w] : k;
+        }
+        bmax[blockIdx.x] = u;
+        bcnt[blockIdx.x] = k;
+    }
+}
+#undef SLAM_FS_STAGE_SCAN
 
 }  // namespace slam

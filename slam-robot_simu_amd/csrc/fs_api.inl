@@ -1,6 +1,6 @@
 // fs_api.inl -- C-ABI of FastSLAM 1.0, with known data association or with
 // per-particle maximum-likelihood association, and of FastSLAM 2.0's proposal
-// handles (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
+// handles, with known ids or associating (include/slam_hip.h, slam_fs_*).  Included by pf_api.hip, as
 // pf_dist_api.inl is: the poses, weights, exact cumsum, systematic resampling,
 // predict and step end are the single handle's own (a slam_pf with zero
 // landmarks); this file adds the per-particle maps, their update with its log
@@ -233,6 +233,35 @@ int fs_enqueue_proposal(slam_fs* f, const double* control, int32_t k, const FsOb
     return SLAM_OK;
 }
 
+// fs_enqueue_proposal on a handle that also associates (fs_assoc_proposal_kernel):
+// the choices always go to memory -- the kernel's second pass reads them back.
+int fs_enqueue_assoc_proposal(slam_fs* f, const double* control, int32_t k, const FsObs* obs,
+                              const double* noise) {
+    slam_pf* h = f->pf;
+    int rc;
+    if ((rc = fs_reserve_assoc(f, k))) return rc;
+    if ((rc = stage_inputs(h, control, nullptr, noise, std::nan("")))) return rc;
+    const int src = h->cur, dst = 1 - h->cur;
+    ++f->call;
+    fs_tic(f, 1);
+#define SLAM_FS_ASSOC_PROPOSAL(HN)                                                               \
+    fs_assoc_proposal_kernel<HN><<<f->nb, kFsThreads, 0, h->stream>>>(                           \
+        f->n, f->npad, h->x[src], h->y[src], h->th[src], h->x[dst], h->y[dst], h->th[dst],       \
+        h->w_un, h->s_cur, h->pc.np_recip, f->map[f->mcur], f->cnt[f->ccur], f->stamp, f->call,  \
+        f->nl, k, obs, f->cfg.use_orient, h->pc.dt, control[0], control[1], f->propq,            \
+        f->acfg.log_p_new, h->noise, (uint32_t)h->stepno, h->cfg.seed, f->assoc_dev,             \
+        f->prop_rec, f->L, f->bmax, f->bcnt)
+    if (noise) SLAM_FS_ASSOC_PROPOSAL(true); else SLAM_FS_ASSOC_PROPOSAL(false);
+#undef SLAM_FS_ASSOC_PROPOSAL
+    fs_toc(f, 1);
+    SLAM_HIP_TRY(hipGetLastError());
+    h->cur = dst;
+    f->prop_ran = true;
+    if ((rc = set_s_one(h))) return rc;
+    h->stepno++;
+    return SLAM_OK;
+}
+
 // the per-particle map update with its log weights, the weights, then the
 // single handle's step end on the current particles (its update stage with
 // zero landmarks: the block partials of the new w_un, then the finalize)
@@ -240,7 +269,13 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
     slam_pf* h = f->pf;
     int rc;
     fs_tic(f, 2);
-    if (k > 0 && f->assoc) {
+    if (k > 0 && f->assoc && f->prop) {
+        // the proposal launch left L, the counts and their block maxima, and updated the maps
+        fs_assoc_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->bcnt, f->nb, f->bmax + f->nb,
+                                                             f->cmax_pin_dev);
+        fs_weight_kernel<<<f->nb, kFsThreads, 0, h->stream>>>(f->n, f->L, f->bmax + f->nb, h->w_un);
+        SLAM_HIP_TRY(hipGetLastError());
+    } else if (k > 0 && f->assoc) {
         const int c = h->cur;
         int32_t* rec = nullptr;
         if (f->acfg.record) {
@@ -301,8 +336,9 @@ int fs_step_records(slam_fs* f, const double* control, int32_t k, const FsObs* d
     const int32_t resampling = h->resample_next;
     int rc;
     if (resampling && (rc = fs_enqueue_resample(f, u))) return rc;
-    if ((rc = f->prop ? fs_enqueue_proposal(f, control, k, dev_obs, noise)
-                      : fs_enqueue_predict(f, control, noise)))
+    if ((rc = f->prop && f->assoc ? fs_enqueue_assoc_proposal(f, control, k, dev_obs, noise)
+              : f->prop         ? fs_enqueue_proposal(f, control, k, dev_obs, noise)
+                                : fs_enqueue_predict(f, control, noise)))
         return rc;
     if ((rc = fs_enqueue_update(f, k, dev_obs, resampling))) return rc;
     if (f->assoc) {
@@ -405,6 +441,24 @@ int slam_fs_create_proposal(const slam_fs_config* cfg, const slam_fs_proposal_co
     SLAM_ARG_CHECK(cfg->pf.motion == SLAM_MOTION_LINEAR,
                    "slam_fs_create_proposal: pf.motion must be SLAM_MOTION_LINEAR");
     return fs_create_impl(cfg, nullptr, pcfg, n_particles, n_landmarks, device, out);
+}
+
+int slam_fs_create_assoc_proposal(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
+                                  const slam_fs_proposal_config* pcfg, int64_t n_particles,
+                                  int32_t max_landmarks, int device, slam_fs** out) {
+    SLAM_ARG_CHECK(cfg, "slam_fs_create_assoc_proposal: NULL cfg");
+    SLAM_ARG_CHECK(acfg, "slam_fs_create_assoc_proposal: NULL acfg");
+    SLAM_ARG_CHECK(pcfg, "slam_fs_create_assoc_proposal: NULL pcfg");
+    SLAM_ARG_CHECK(out, "slam_fs_create_assoc_proposal: NULL out");
+    *out = nullptr;
+    SLAM_ARG_CHECK(n_particles >= 1 && n_particles <= (int64_t(1) << 24),
+                   "slam_fs_create_assoc_proposal: need 1 <= n_particles <= 2^24");
+    SLAM_ARG_CHECK(max_landmarks >= 1, "slam_fs_create_assoc_proposal: need max_landmarks >= 1");
+    SLAM_ARG_CHECK(std::isfinite(acfg->log_p_new),
+                   "slam_fs_create_assoc_proposal: non-finite log_p_new");
+    SLAM_ARG_CHECK(cfg->pf.motion == SLAM_MOTION_LINEAR,
+                   "slam_fs_create_assoc_proposal: pf.motion must be SLAM_MOTION_LINEAR");
+    return fs_create_impl(cfg, acfg, pcfg, n_particles, max_landmarks, device, out);
 }
 
 }  // extern "C"
@@ -752,7 +806,9 @@ int slam_fs_get_counts(slam_fs* f, int32_t* counts) {
 int slam_fs_get_assoc(slam_fs* f, int32_t* out) {
     SLAM_ARG_CHECK(f && out, "slam_fs_get_assoc: NULL argument");
     SLAM_ARG_CHECK(f->assoc, "slam_fs_get_assoc: not an associating handle");
-    SLAM_ARG_CHECK(f->acfg.record, "slam_fs_get_assoc: the handle does not record (record = 0)");
+    // a proposal handle's kernel keeps the choices between its passes whatever record says
+    SLAM_ARG_CHECK(f->acfg.record || f->prop,
+                   "slam_fs_get_assoc: the handle does not record (record = 0)");
     if (f->assoc_k == 0) return SLAM_OK;
     SLAM_HIP_TRY(hipSetDevice(f->pf->device));
     SLAM_HIP_TRY(hipMemcpy2DAsync(out, sizeof(int32_t) * (size_t)f->n, f->assoc_dev,

@@ -67,7 +67,10 @@ class FastSLAM:
     it from the resulting N(mu, Sigma).  ``step``'s ``noise`` then means three
     standard normals per particle ([NP][3], pose = mu + chol(Sigma) noise), not
     the Q-shaped motion noise of the default proposal; ``record_proposal``
-    keeps mu, Sigma and the log weights for ``dev.last_proposal()``."""
+    keeps mu, Sigma and the log weights for ``dev.last_proposal()``.
+    ``association="ml_marginal"`` with ``proposal="measurement"``: FastSLAM 2.0
+    from scans without ids -- the association runs inside the proposal, its
+    score marginalising the pose; ``n_landmarks`` is the capacity."""
 
     def __init__(self, n_particles, n_landmarks, **kw):
         self.dev = DeviceFastSLAM(n_particles, n_landmarks, **kw)
@@ -79,7 +82,7 @@ class FastSLAM:
         weighted particle covariance.  The motion noise and the resampling
         offset come from the device RNG unless given (as slam_pf_step)."""
         ids, obs = _split(observations)
-        if self.dev.association == "ml":
+        if self.dev.association in ("ml", "ml_marginal"):
             ids = None
         self.last = self.dev.step(control, ids, obs, noise, u_resample)
         return self.last["x_est"], self.last["cov"], self.dev.best_map()

@@ -233,6 +233,9 @@ SIGNATURES = {
     "slam_fs_create_proposal": (C.c_int, [C.POINTER(FSConfig), C.POINTER(FSProposalConfig), C.c_int64,
                                           C.c_int32, C.c_int, C.POINTER(_P)]),
     "slam_fs_get_proposal": (C.c_int, [_P, _D, _D, _D]),
+    "slam_fs_create_assoc_proposal": (C.c_int, [C.POINTER(FSConfig), C.POINTER(FSAssocConfig),
+                                                C.POINTER(FSProposalConfig), C.c_int64, C.c_int32,
+                                                C.c_int, C.POINTER(_P)]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

@@ -21,6 +21,11 @@ motion) a step filters every particle's pose through the scan before drawing
 it: the pose comes from N(mu, Sigma) with the scan's seen landmarks folded in,
 and the weight no longer depends on the draw.  ``noise`` is then three
 standard normals per particle, not Q-shaped noise.
+
+With ``association="ml_marginal"`` (which needs ``proposal="measurement"``)
+the two go together, FastSLAM 2.0 without ids: every particle associates
+inside its proposal, the score of a candidate marginalising the pose
+uncertainty the proposal still has; ``n_landmarks`` is again the capacity.
 """
 from __future__ import annotations
 
@@ -60,7 +65,10 @@ class DeviceFastSLAM:
     every observation) or "ml" (per-particle maximum likelihood: ``ids`` is
     None everywhere, ``n_landmarks`` is the capacity of a particle's map,
     ``p_new`` the likelihood below which an observation starts a new landmark,
-    ``record_assoc`` keeps each update's choices for ``last_assoc``).
+    ``record_assoc`` keeps each update's choices for ``last_assoc``), or
+    "ml_marginal" (the same without ids under ``proposal="measurement"``,
+    which it requires: the score folds the proposal's pose covariance into S;
+    ``last_assoc`` works whatever ``record_assoc`` says).
     ``proposal``: "motion" (FastSLAM 1.0: the pose from the motion model) or
     "measurement" (FastSLAM 2.0: the pose from the proposal that has seen the
     scan; ``step``'s ``noise`` is then [NP][3] standard normals, ``predict`` and
@@ -76,12 +84,15 @@ class DeviceFastSLAM:
                  ess_threshold=None, seed=0, device=0, association="known",
                  p_new=P_NEW_DEFAULT, record_assoc=False, proposal="motion",
                  record_proposal=False):
-        if association not in ("known", "ml"):
-            raise ValueError("association: 'known' or 'ml'")
+        if association not in ("known", "ml", "ml_marginal"):
+            raise ValueError("association: 'known', 'ml' or 'ml_marginal'")
         if proposal not in _lib.FS_PROPOSAL:
             raise ValueError("proposal: 'motion' or 'measurement'")
         if proposal == "measurement" and association == "ml":
-            raise ValueError("proposal='measurement' needs association='known'")
+            raise ValueError("proposal='measurement' needs association='known' or 'ml_marginal' "
+                             "(the score that marginalises the pose)")
+        if association == "ml_marginal" and proposal != "measurement":
+            raise ValueError("association='ml_marginal' needs proposal='measurement'")
         lib = _lib.load()
         self.n = int(n_particles)
         self.nl = int(n_landmarks)
@@ -98,13 +109,19 @@ class DeviceFastSLAM:
         self.record_proposal = bool(record_proposal)
         self._last_k = 0
         h = C.c_void_p()
-        if association == "ml":
+        if association in ("ml", "ml_marginal"):
             if not p_new > 0:
                 raise ValueError("p_new must be positive")
             acfg = FSAssocConfig(float(np.log(p_new)), int(self.record_assoc), 0)
             self.acfg = acfg
+        if association == "ml":
             check(lib.slam_fs_create_assoc(C.byref(cfg), C.byref(acfg), self.n, self.nl, int(device),
                                            C.byref(h)), "slam_fs_create_assoc")
+        elif association == "ml_marginal":
+            pcfg = FSProposalConfig(int(self.record_proposal), 0)
+            check(lib.slam_fs_create_assoc_proposal(C.byref(cfg), C.byref(acfg), C.byref(pcfg),
+                                                    self.n, self.nl, int(device), C.byref(h)),
+                  "slam_fs_create_assoc_proposal")
         elif proposal == "measurement":
             pcfg = FSProposalConfig(int(self.record_proposal), 0)
             check(lib.slam_fs_create_proposal(C.byref(cfg), C.byref(pcfg), self.n, self.nl,
