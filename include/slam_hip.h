@@ -533,7 +533,7 @@ int slam_fs_timing(slam_fs* h, double* out);
  * handle lets every particle decide for itself which of its own landmarks an
  * observation belongs to.  Particle p holds cnt_p <= cap landmarks in slots
  * 0..cnt_p-1 of its map, in the order it created them; landmarks are never
- * removed.
+ * removed unless the handle prunes (slam_fs_set_pruning, below; off by default).
  *
  * A step keeps the order above; resample, predict and the step end are
  * unchanged (the gather moves the counts with the poses, and the map rows
@@ -581,7 +581,8 @@ int slam_fs_set_counts(slam_fs* h, const int32_t* counts);
 int slam_fs_get_counts(slam_fs* h, int32_t* counts);
 /* out[k][NP], k of the last update (of slam_fs_run: its last step): the slot
  * matched, -1 for a new landmark, -2 for a dropped observation.  SLAM_ERR_ARG
- * unless the handle was created with record != 0. */
+ * unless the handle was created with record != 0.  On a pruning handle the
+ * slot numbers are those in force during the update, before the compaction. */
 int slam_fs_get_assoc(slam_fs* h, int32_t* out);
 
 /* --------------------------------------------------------------------
@@ -714,6 +715,70 @@ int slam_fs_get_proposal(slam_fs* h, double* mean, double* cov, double* L);
 int slam_fs_create_assoc_proposal(const slam_fs_config* cfg, const slam_fs_assoc_config* acfg,
                                   const slam_fs_proposal_config* pcfg, int64_t n_particles,
                                   int32_t max_landmarks, int device, slam_fs** out);
+
+/* --------------------------------------------------------------------
+ * Landmark evidence and removal of unsupported landmarks: an optional mode of
+ * both associating handle kinds, off by default (a handle that never turns it
+ * on launches what it launched before, with the same arguments).  Each slot
+ * j < cnt_p of each particle carries an int32 evidence value ev_p[j].
+ *
+ * The pruning pass runs after the map update (steps 3 and 4 of the contracts
+ * above), on every slam_fs_step and stand-alone slam_fs_update, k = 0
+ * included: an empty scan is evidence too.  For particle p let cnt0_p be the
+ * count before the update, cnt_p the count after it, and (x, y, th) the
+ * particle's current pose (after predict on a slam_fs_create_assoc handle, the
+ * sampled pose on a slam_fs_create_assoc_proposal handle).  For every slot
+ * j < cnt_p, in slot order:
+ *   1. j >= cnt0_p (created by this update): ev = init;
+ *   2. an observation of this update matched the slot: ev = min(ev + hit, ev_max);
+ *   3. otherwise, with (mx, my) the slot's mean: dx = mx - x, dy = my - y, and
+ *      with c, s = cos, sin(pi/2 - th): rx = c dx - s dy, ry = s dx + c dy.
+ *      The landmark is in view when dx dx + dy dy <= view_range view_range and,
+ *      with use_angle, also ry >= |rx| view_tan; a comparison with a NaN counts
+ *      as not in view.  In view: ev -= miss (the value saturates at INT32_MIN);
+ *      out of view: unchanged;
+ *   4. slots with ev < remove_below are removed: the surviving slots keep their
+ *      order and move down to slots 0..cnt'_p-1 with their mean, covariance and
+ *      evidence, bit for bit; cnt_p = cnt'_p, and removed_p is the difference.
+ * The weights of the step do not depend on the pass.  Resampling gathers the
+ * evidence rows with the maps, so the copies of a particle share them.
+ * slam_fs_get_assoc's slot numbers are those in force during the update,
+ * before the compaction; slam_fs_info, slam_fs_get_counts and the map
+ * accessors report the state after the pass.  slam_fs_run equals slam_fs_step
+ * in turn, pass included.  slam_fs_timing keeps its four phases: the pass
+ * belongs to phase 2, the evidence gather to phase 0.
+ *
+ * slam_fs_set_pruning may be called between steps any number of times; NULL
+ * turns the mode off.  Turning it on (from off) gives every live slot init and
+ * clears removed; a call on a handle that is already pruning only replaces the
+ * configuration.  The first turning on allocates 2 x 4 B x cap x n_particles
+ * of evidence (SLAM_ERR_HIP if that does not fit).  slam_fs_set_counts on a
+ * pruning handle resets the live slots to init; slam_fs_set_evidence then
+ * overrides.  SLAM_ERR_ARG: a known-association handle, a bad configuration
+ * (before any HIP call), and from the three accessors while pruning is off.
+ * -------------------------------------------------------------------- */
+typedef struct {
+    double  view_range;    /* > 0, finite: a landmark counts as in view up to this range of the particle */
+    double  view_tan;      /* used when use_angle: in view iff ry >= |rx| * view_tan (ScanSensor's
+                              fan of half-angle a: view_tan = tan(pi/2 - a)); not NaN then */
+    int32_t use_angle;     /* 0: range only */
+    int32_t init, hit, miss;      /* evidence of a new landmark; added on a match; subtracted on
+                                     an in-view miss (hit, miss >= 0) */
+    int32_t ev_max;        /* evidence saturates here (>= init) */
+    int32_t remove_below;  /* a landmark whose evidence is < this after the step is removed
+                              (init >= remove_below) */
+} slam_fs_prune_config;
+
+/* Host only, like slam_fs_check_observations: SLAM_ERR_ARG for NULL, a
+ * non-finite or <= 0 view_range, a NaN view_tan with use_angle, hit < 0 or
+ * miss < 0, ev_max < init, init < remove_below. */
+int slam_fs_check_prune_config(const slam_fs_prune_config* cfg);
+int slam_fs_set_pruning(slam_fs* h, const slam_fs_prune_config* cfg);
+/* ev[NP][cap]; the slots j >= cnt_p are ignored by set and 0 from get */
+int slam_fs_set_evidence(slam_fs* h, const int32_t* ev);
+int slam_fs_get_evidence(slam_fs* h, int32_t* ev);
+/* removed[NP]: the last pass's removals per particle (0 before any pass) */
+int slam_fs_get_removed(slam_fs* h, int32_t* removed);
 
 /* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve

@@ -4,8 +4,13 @@
 // pf_dist_api.inl is: the poses, weights, exact cumsum, systematic resampling,
 // predict and step end are the single handle's own (a slam_pf with zero
 // landmarks); this file adds the per-particle maps, their update with its log
-// weights, and their resampling gather (fastslam.inl).
+// weights, and their resampling gather (fastslam.inl), and the optional landmark
+// evidence pass (fs_prune.hip).
 #include "fastslam.inl"
+#include "fs_prune.hpp"
+
+static_assert(slam::kFsPruneThreads == slam::kFsThreads && slam::kFsPruneComp == slam::kFsComp,
+              "fs_prune.hip walks fastslam.inl's layout");
 
 struct slam_fs {
     slam_fs_config cfg;
@@ -50,6 +55,13 @@ struct slam_fs {
     FsPropQ propq = {};                    // Q = F^T F of cfg.pf.q_factor
     double* prop_rec = nullptr;            // [9][npad] mean and covariance before sampling (record)
     bool prop_ran = false;                 // a step has filled prop_rec and L
+    // landmark evidence and removal (slam_fs_set_pruning); buffers from the first turning on
+    bool prune = false;
+    slam_fs_prune_config prcfg = {};
+    int32_t* evd[2] = {nullptr, nullptr};  // ping-pong halves of the evidence, [cap][npad]
+    int ecur = 0;
+    int32_t* cnt0 = nullptr;               // [npad] the counts ahead of the update
+    int32_t* removed = nullptr;            // [npad] the last pass's removals
 };
 
 namespace {
@@ -165,6 +177,12 @@ int fs_enqueue_resample(slam_fs* f, double u) {
         fs_assoc_gather_kernel<<<fs_grid(f->n, f->cmax), kFsThreads, 0, h->stream>>>(
             f->n, f->npad, h->idx, f->cmax, f->map[f->mcur], f->map[1 - f->mcur], f->cnt[f->ccur],
             f->cnt[1 - f->ccur]);
+        if (f->prune) {
+            // the evidence rows with the maps, by the source's counts
+            fs_prune_gather_launch(h->stream, fs_grid(f->n, f->cmax), f->n, f->npad, h->idx, f->cmax,
+                                   f->cnt[f->ccur], f->evd[f->ecur], f->evd[1 - f->ecur]);
+            f->ecur = 1 - f->ecur;
+        }
         SLAM_HIP_TRY(hipGetLastError());
         f->mcur = 1 - f->mcur;
         f->ccur = 1 - f->ccur;
@@ -188,6 +206,31 @@ int fs_enqueue_resample(slam_fs* f, double u) {
     fs_toc(f, 0);
     h->resample_next = 0;
     return set_flag(h, kFlagResample, 0);
+}
+
+// A pruning handle: the counts as they stand ahead of the map update (the
+// update kernels overwrite them in place; the pass needs cnt0 -- DESIGN 11f)
+int fs_prune_note_counts(slam_fs* f) {
+    if (!f->prune) return SLAM_OK;
+    SLAM_HIP_TRY(hipMemcpyAsync(f->cnt0, f->cnt[f->ccur], sizeof(int32_t) * (size_t)f->npad,
+                                hipMemcpyDeviceToDevice, f->pf->stream));
+    return SLAM_OK;
+}
+
+// The evidence pass after the map update, then the largest count to the host's
+// coherent word.  call: the update's number, -1 where no update ran (k = 0 on
+// an "ml" handle: no stamp equals it).
+int fs_enqueue_prune(slam_fs* f, int32_t call) {
+    slam_pf* h = f->pf;
+    const slam_fs_prune_config& pc = f->prcfg;
+    const FsPrune P{pc.view_range * pc.view_range, pc.view_tan, pc.init, pc.hit, pc.miss,
+                    pc.ev_max, pc.remove_below};
+    const int c = h->cur;
+    fs_prune_launch(h->stream, pc.use_angle != 0, f->nb, f->n, f->npad, h->x[c], h->y[c], h->th[c],
+                    f->map[f->mcur], f->cnt[f->ccur], f->cnt0, f->stamp, call, f->nl, P,
+                    f->evd[f->ecur], f->removed, f->bcnt, f->cmax_pin_dev);
+    SLAM_HIP_TRY(hipGetLastError());
+    return SLAM_OK;
 }
 
 // __predict (particle_filter.py:156-168): the single handle's fused launch
@@ -241,6 +284,7 @@ int fs_enqueue_assoc_proposal(slam_fs* f, const double* control, int32_t k, cons
     int rc;
     if ((rc = fs_reserve_assoc(f, k))) return rc;
     if ((rc = stage_inputs(h, control, nullptr, noise, std::nan("")))) return rc;
+    if ((rc = fs_prune_note_counts(f))) return rc;
     const int src = h->cur, dst = 1 - h->cur;
     ++f->call;
     fs_tic(f, 1);
@@ -269,6 +313,7 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
     slam_pf* h = f->pf;
     int rc;
     fs_tic(f, 2);
+    if (!f->prop && (rc = fs_prune_note_counts(f))) return rc;     // a proposal launch took its own
     if (k > 0 && f->assoc && f->prop) {
         // the proposal launch left L, the counts and their block maxima, and updated the maps
         fs_assoc_fold_kernel<<<1, kFsThreads, 0, h->stream>>>(f->bmax, f->bcnt, f->nb, f->bmax + f->nb,
@@ -307,6 +352,8 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
         SLAM_HIP_TRY(hipGetLastError());
     }
     if (f->assoc) f->assoc_k = k;
+    // an empty scan is evidence too: the pass runs whatever k is
+    if (f->prune && (rc = fs_enqueue_prune(f, k > 0 || f->prop ? f->call : -1))) return rc;
     fs_toc(f, 2);
     static const double ctl0[2] = {0.0, 0.0};
     SLAM_HIP_TRY(hipMemcpyAsync(h->ctl, ctl0, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -321,7 +368,7 @@ int fs_enqueue_update(slam_fs* f, int32_t k, const FsObs* obs, int32_t resampled
 // "seen": it takes the largest count, which the fold stored beside the record.
 void fs_note_seen(slam_fs* f, int32_t k, const FsObs* obs) {
     if (f->assoc) {
-        if (k > 0) f->cmax = *f->cmax_pin;
+        if (k > 0 || f->prune) f->cmax = *f->cmax_pin;     // a pruning pass folds on every step
         return;
     }
     for (int32_t t = 0; t < k; ++t) f->seen[(size_t)obs[t].id] = 1;
@@ -557,6 +604,14 @@ int fs_counts_host(slam_fs* f, std::vector<int32_t>& c) {
     return SLAM_OK;
 }
 
+// every slot of the current evidence half at init (the slots at or above a
+// particle's count are never read: a slot the update creates takes init)
+int fs_evidence_init(slam_fs* f) {
+    SLAM_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)f->evd[f->ecur], f->prcfg.init,
+                                   (size_t)f->nl * (size_t)f->npad, f->pf->stream));
+    return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -788,8 +843,101 @@ int slam_fs_set_counts(slam_fs* f, const int32_t* counts) {
     SLAM_HIP_TRY(hipSetDevice(f->pf->device));
     SLAM_HIP_TRY(hipMemcpyAsync(f->cnt[f->ccur], counts, sizeof(int32_t) * (size_t)f->n,
                                 hipMemcpyHostToDevice, f->pf->stream));
+    if (f->prune) {
+        const int rc = fs_evidence_init(f);     // the slots that now hold start at init
+        if (rc) return rc;
+    }
     SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
     f->cmax = cm;
+    return SLAM_OK;
+}
+
+int slam_fs_check_prune_config(const slam_fs_prune_config* c) {
+    SLAM_ARG_CHECK(c, "slam_fs_check_prune_config: NULL config");
+    SLAM_ARG_CHECK(std::isfinite(c->view_range) && c->view_range > 0.0,
+                   "slam_fs_check_prune_config: need a finite view_range > 0");
+    SLAM_ARG_CHECK(!c->use_angle || !std::isnan(c->view_tan),
+                   "slam_fs_check_prune_config: view_tan is NaN");
+    SLAM_ARG_CHECK(c->hit >= 0 && c->miss >= 0, "slam_fs_check_prune_config: need hit, miss >= 0");
+    SLAM_ARG_CHECK(c->ev_max >= c->init, "slam_fs_check_prune_config: need ev_max >= init");
+    SLAM_ARG_CHECK(c->init >= c->remove_below,
+                   "slam_fs_check_prune_config: need init >= remove_below");
+    return SLAM_OK;
+}
+
+int slam_fs_set_pruning(slam_fs* f, const slam_fs_prune_config* c) {
+    SLAM_ARG_CHECK(f, "slam_fs_set_pruning: NULL handle");
+    SLAM_ARG_CHECK(f->assoc, "slam_fs_set_pruning: not an associating handle");
+    if (!c) {
+        f->prune = false;
+        return SLAM_OK;
+    }
+    int rc = slam_fs_check_prune_config(c);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    if (!f->evd[0]) {
+        const size_t rows = (size_t)f->nl * (size_t)f->npad;
+        if ((rc = f->mem.alloc(&f->evd[0], rows)) || (rc = f->mem.alloc(&f->evd[1], rows)) ||
+            (rc = f->mem.alloc(&f->cnt0, (size_t)f->npad)) ||
+            (rc = f->mem.alloc(&f->removed, (size_t)f->npad))) {
+            f->mem.release(f->evd[0]);
+            f->mem.release(f->evd[1]);
+            f->mem.release(f->cnt0);
+            f->mem.release(f->removed);
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    const bool was = f->prune;
+    f->prcfg = *c;
+    f->prcfg.use_angle = c->use_angle ? 1 : 0;
+    f->prune = true;
+    if (!was) {
+        // turned on: every live slot starts at init, nothing removed yet
+        if ((rc = fs_evidence_init(f))) return rc;
+        SLAM_HIP_TRY(hipMemsetAsync(f->removed, 0, sizeof(int32_t) * (size_t)f->npad, f->pf->stream));
+        SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    }
+    return SLAM_OK;
+}
+
+int slam_fs_set_evidence(slam_fs* f, const int32_t* ev) {
+    SLAM_ARG_CHECK(f && ev, "slam_fs_set_evidence: NULL argument");
+    SLAM_ARG_CHECK(f->prune, "slam_fs_set_evidence: pruning is off");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    const size_t npad = (size_t)f->npad, nl = (size_t)f->nl;
+    std::vector<int32_t> rows(nl * npad, f->prcfg.init);
+    for (size_t p = 0; p < (size_t)f->n; ++p)
+        for (size_t j = 0; j < nl; ++j) rows[j * npad + p] = ev[p * nl + j];
+    SLAM_HIP_TRY(hipMemcpyAsync(f->evd[f->ecur], rows.data(), sizeof(int32_t) * rows.size(),
+                                hipMemcpyHostToDevice, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
+    return SLAM_OK;
+}
+
+int slam_fs_get_evidence(slam_fs* f, int32_t* ev) {
+    SLAM_ARG_CHECK(f && ev, "slam_fs_get_evidence: NULL argument");
+    SLAM_ARG_CHECK(f->prune, "slam_fs_get_evidence: pruning is off");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    const size_t npad = (size_t)f->npad, nl = (size_t)f->nl;
+    std::vector<int32_t> rows(nl * npad), c;
+    SLAM_HIP_TRY(hipMemcpyAsync(rows.data(), f->evd[f->ecur], sizeof(int32_t) * rows.size(),
+                                hipMemcpyDeviceToHost, f->pf->stream));
+    const int rc = fs_counts_host(f, c);        // synchronises
+    if (rc) return rc;
+    for (size_t p = 0; p < (size_t)f->n; ++p)
+        for (size_t j = 0; j < nl; ++j)
+            ev[p * nl + j] = (int32_t)j < c[p] ? rows[j * npad + p] : 0;
+    return SLAM_OK;
+}
+
+int slam_fs_get_removed(slam_fs* f, int32_t* removed) {
+    SLAM_ARG_CHECK(f && removed, "slam_fs_get_removed: NULL argument");
+    SLAM_ARG_CHECK(f->prune, "slam_fs_get_removed: pruning is off");
+    SLAM_HIP_TRY(hipSetDevice(f->pf->device));
+    SLAM_HIP_TRY(hipMemcpyAsync(removed, f->removed, sizeof(int32_t) * (size_t)f->n,
+                                hipMemcpyDeviceToHost, f->pf->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(f->pf->stream));
     return SLAM_OK;
 }
 

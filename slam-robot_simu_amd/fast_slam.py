@@ -34,6 +34,19 @@ particle matches an observation to the likeliest landmark of its own map, or
 starts a new one (``p_new``), and ``best_map()`` is the heaviest particle's
 ``(seen, mean, cov)`` with ``seen[j] = j < count``.  ``step`` then also accepts
 ``(None, obs)``.
+
+Such a filter also starts landmarks that are not there (a noisy sighting that
+matches nothing), and by itself never takes one away.  ``prune=dict(
+view_range=7.2)`` adds the existence counter of published FastSLAM: a landmark
+gains evidence when it is matched, loses it when it lies in view and the scan
+did not contain it, and leaves the map below a threshold (``init``, ``hit``,
+``miss``, ``ev_max``, ``remove_below``, ``view_angle``: DeviceFastSLAM.
+set_pruning).  Give a view range somewhat inside the sensor's -- 7.2 m for the
+9 m sensor above -- so that a landmark at the edge of the range, which the
+sensor may or may not return, is not counted as missed::
+
+    slam = FastSLAM(4096, 32, association="ml", p_new=0.1,
+                    prune=dict(view_range=7.2), ess_threshold=2048, seed=1)
 """
 from __future__ import annotations
 
@@ -70,7 +83,10 @@ class FastSLAM:
     keeps mu, Sigma and the log weights for ``dev.last_proposal()``.
     ``association="ml_marginal"`` with ``proposal="measurement"``: FastSLAM 2.0
     from scans without ids -- the association runs inside the proposal, its
-    score marginalising the pose; ``n_landmarks`` is the capacity."""
+    score marginalising the pose; ``n_landmarks`` is the capacity.
+    ``prune=dict(view_range=..., ...)`` (associating kinds only): landmark
+    evidence and the removal of unsupported landmarks; ``best_map()`` is the
+    compacted map."""
 
     def __init__(self, n_particles, n_landmarks, **kw):
         self.dev = DeviceFastSLAM(n_particles, n_landmarks, **kw)

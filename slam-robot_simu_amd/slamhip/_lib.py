@@ -82,6 +82,12 @@ class FSProposalConfig(C.Structure):
 FS_PROPOSAL = ("motion", "measurement")     # DeviceFastSLAM(proposal=...)
 
 
+class FSPruneConfig(C.Structure):
+    _fields_ = [("view_range", C.c_double), ("view_tan", C.c_double), ("use_angle", C.c_int32),
+                ("init", C.c_int32), ("hit", C.c_int32), ("miss", C.c_int32),
+                ("ev_max", C.c_int32), ("remove_below", C.c_int32)]
+
+
 class GraphEdge(C.Structure):
     _fields_ = [("time_bfr", C.c_int64), ("pose_bfr", C.c_int64), ("time_aft", C.c_int64),
                 ("pose_aft", C.c_int64), ("obs_bfr", C.c_double * 3), ("obs_aft", C.c_double * 3)]
@@ -236,6 +242,11 @@ SIGNATURES = {
     "slam_fs_create_assoc_proposal": (C.c_int, [C.POINTER(FSConfig), C.POINTER(FSAssocConfig),
                                                 C.POINTER(FSProposalConfig), C.c_int64, C.c_int32,
                                                 C.c_int, C.POINTER(_P)]),
+    "slam_fs_check_prune_config": (C.c_int, [C.POINTER(FSPruneConfig)]),
+    "slam_fs_set_pruning": (C.c_int, [_P, C.POINTER(FSPruneConfig)]),
+    "slam_fs_set_evidence": (C.c_int, [_P, _I32]),
+    "slam_fs_get_evidence": (C.c_int, [_P, _I32]),
+    "slam_fs_get_removed": (C.c_int, [_P, _I32]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

@@ -26,6 +26,12 @@ With ``association="ml_marginal"`` (which needs ``proposal="measurement"``)
 the two go together, FastSLAM 2.0 without ids: every particle associates
 inside its proposal, the score of a candidate marginalising the pose
 uncertainty the proposal still has; ``n_landmarks`` is again the capacity.
+
+Either associating kind can prune (``prune=dict(view_range=...)``): every
+landmark carries an evidence counter, raised when an observation matches it and
+lowered when it lies in the sensor's view unmatched, and is removed from its
+particle's map once the counter falls below a threshold (the contract is in
+include/slam_hip.h, the kernel fs_prune_kernel).
 """
 from __future__ import annotations
 
@@ -34,7 +40,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FSAssocConfig, FSConfig, FSProposalConfig, PFResult, check, dptr
+from ._lib import (FSAssocConfig, FSConfig, FSProposalConfig, FSPruneConfig, PFResult, check,
+                   dptr)
 from .pf import DeviceParticleFilter, RunResults, _f64, make_config
 
 
@@ -57,6 +64,20 @@ def _iptr(ids):
     return None if ids is None else ids.ctypes.data_as(_lib._I64)
 
 
+def prune_config(view_range, view_angle=None, init=1, hit=1, miss=1, ev_max=2 ** 31 - 1,
+                 remove_below=0):
+    """slam_fs_prune_config from the front end's keywords.  ``view_angle`` is
+    the half-angle of the sensor's fan as ScanSensor takes it (None: range
+    only); the C-ABI gets tan(pi/2 - view_angle)."""
+    c = FSPruneConfig()
+    c.view_range = float(view_range)
+    c.use_angle = int(view_angle is not None)
+    c.view_tan = float(np.tan(np.pi / 2 - view_angle)) if c.use_angle else 0.0
+    c.init, c.hit, c.miss = int(init), int(hit), int(miss)
+    c.ev_max, c.remove_below = int(ev_max), int(remove_below)
+    return c
+
+
 class DeviceFastSLAM:
     """Particles with per-particle landmark maps on one GPU.
 
@@ -73,8 +94,10 @@ class DeviceFastSLAM:
     "measurement" (FastSLAM 2.0: the pose from the proposal that has seen the
     scan; ``step``'s ``noise`` is then [NP][3] standard normals, ``predict`` and
     ``update`` raise, ``record_proposal`` keeps each step's mean, covariance
-    and log weight for ``last_proposal``).  The other keywords are
-    DeviceParticleFilter's."""
+    and log weight for ``last_proposal``).  ``prune``: None, or ``set_pruning``'s
+    keywords as a dict (associating handles only): landmarks carry an evidence
+    counter and those the scans stop supporting are removed.  The other
+    keywords are DeviceParticleFilter's."""
 
     ESS_CONFIRM_BAND = DeviceParticleFilter.ESS_CONFIRM_BAND
 
@@ -83,9 +106,11 @@ class DeviceFastSLAM:
                  noise=(0.1, np.deg2rad(3.0), np.deg2rad(3.0)), use_orient=True,
                  ess_threshold=None, seed=0, device=0, association="known",
                  p_new=P_NEW_DEFAULT, record_assoc=False, proposal="motion",
-                 record_proposal=False):
+                 record_proposal=False, prune=None):
         if association not in ("known", "ml", "ml_marginal"):
             raise ValueError("association: 'known', 'ml' or 'ml_marginal'")
+        if prune is not None and association == "known":
+            raise ValueError("prune needs association='ml' or 'ml_marginal'")
         if proposal not in _lib.FS_PROPOSAL:
             raise ValueError("proposal: 'motion' or 'measurement'")
         if proposal == "measurement" and association == "ml":
@@ -135,6 +160,13 @@ class DeviceFastSLAM:
         self.last = None
         self._run_steps = 0
         self._run_counts = np.zeros(0, dtype=np.int32)
+        self.prune = None
+        if prune is not None:
+            try:
+                self.set_pruning(**prune)
+            except Exception:
+                self.close()
+                raise
 
     # ------------------------------------------------------------ lifetime
     def close(self):
@@ -226,6 +258,47 @@ class DeviceFastSLAM:
         check(self._lib.slam_fs_get_assoc(self._h, a.ctypes.data_as(_lib._I32)),
               "slam_fs_get_assoc")
         return a
+
+    def set_pruning(self, view_range=None, **kw):
+        """Landmark evidence and removal on an associating handle
+        (slam_fs_set_pruning): ``set_pruning(view_range, view_angle=None,
+        init=1, hit=1, miss=1, ev_max=2**31 - 1, remove_below=0)`` turns it on
+        (every live slot starts at ``init``) or replaces the configuration;
+        ``set_pruning(None)`` turns it off.  A landmark gains ``hit`` when an
+        observation matches it, loses ``miss`` when it lies within
+        ``view_range`` (and the fan of half-angle ``view_angle``) of the
+        particle unmatched, and is removed below ``remove_below``."""
+        if self.association == "known":
+            raise ValueError("set_pruning needs association='ml' or 'ml_marginal'")
+        if view_range is None:
+            if kw:
+                raise ValueError("set_pruning(None) takes no other argument")
+            check(self._lib.slam_fs_set_pruning(self._h, None), "slam_fs_set_pruning")
+            self.prune = None
+            return
+        cfg = prune_config(view_range, **kw)
+        check(self._lib.slam_fs_set_pruning(self._h, C.byref(cfg)), "slam_fs_set_pruning")
+        self.prune = cfg
+
+    def evidence(self):
+        """The evidence of every slot, [NP][n_landmarks] int32; 0 at and above a
+        particle's count."""
+        e = np.empty((self.n, self.nl), dtype=np.int32)
+        check(self._lib.slam_fs_get_evidence(self._h, e.ctypes.data_as(_lib._I32)),
+              "slam_fs_get_evidence")
+        return e
+
+    def set_evidence(self, ev):
+        e = np.ascontiguousarray(ev, dtype=np.int32).reshape(self.n, self.nl)
+        check(self._lib.slam_fs_set_evidence(self._h, e.ctypes.data_as(_lib._I32)),
+              "slam_fs_set_evidence")
+
+    def last_removed(self):
+        """The landmarks the last step's pass removed, per particle [NP]."""
+        r = np.empty(self.n, dtype=np.int32)
+        check(self._lib.slam_fs_get_removed(self._h, r.ctypes.data_as(_lib._I32)),
+              "slam_fs_get_removed")
+        return r
 
     def last_proposal(self):
         """proposal="measurement", record_proposal=True: the last step's
