@@ -671,12 +671,18 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     if (A(h->bsum, h->nb_part)) return rc;
     if (A(h->boff, h->nb_part + 1)) return rc;
     if (A(h->s_cur, 1)) return rc;
-    if (A(h->dp.pmax, h->nb_part + 1)) return rc;   // + 1: the finalize's pair loads
-    if (A(h->dp.pidx, h->nb_part)) return rc;
-    if (A(h->dp.ppre, h->nb_part)) return rc;
-    for (int q = 0; q < 3; ++q) if (A(h->dp.pxe[q], h->nb_part)) return rc;
-    for (int q = 0; q < 11; ++q) if (A(h->dp.ps[q], h->nb_part + 1)) return rc;
-    if (A(h->dp.leaf, (size_t)(kPartPer / 128) * h->nb_part)) return rc;
+    {
+        // the block partials' slab (DeferParts): + 1 entry for the finalize's
+        // pair loads, rounded to whole 128-byte lines; the leaf array, the
+        // last, also covers the first round of the finalize's leaf loads
+        // (16 entries per buffer lane group, whatever nb_part is)
+        const int64_t stride = ((int64_t)h->nb_part + 1 + 15) / 16 * 16;
+        const int64_t leaf = std::max<int64_t>(stride, 16 * (int64_t)kFinBufPerRound);
+        const int64_t words = (kDeferArrays - 1) * stride + leaf;
+        if (A(h->dp.slab, words)) return rc;
+        h->dp.stride = stride;
+        SLAM_HIP_TRY(hipMemsetAsync(h->dp.slab, 0, sizeof(double) * words, h->stream));
+    }
     if (A(h->dp.mark, npad)) return rc;
     if (A(h->dp.carry, h->nb_part + 1)) return rc;
     if (h->nb_part > kFinThreads * kFinRegBlocks) {

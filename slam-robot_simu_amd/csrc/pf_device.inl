@@ -220,6 +220,32 @@ __device__ __forceinline__ void st_wt_pair(double* p, const double a, const doub
     const f64x2_t v = {a, b};
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
+// The kernel's own argument segment as a struct A (A mirrors the kernel's
+// parameter list, member for member), to read an argument where it is used
+// and not at the kernel's start: a value loaded there occupies scalar registers up to
+// its last use, and the fused kernel has none to spare.  The
+// empty asm hides the address from the compiler, which would otherwise merge
+// these loads with the entry's, and takes `after` (a lane value computed
+// where the view is wanted) as an input, which keeps it and the loads behind
+// that computation.  Not volatile: a volatile asm counts as a write to any
+// address, and the wave-uniform loads of device memory behind it would become
+// per-lane ones.  The segment is constant memory: its loads stay scalar even
+// behind the write-through stores.
+#define SLAM_KARG __attribute__((address_space(4)))
+template <typename A>
+__device__ __forceinline__ const SLAM_KARG A* kernarg_view(const double after) {
+    uint64_t u = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm("" : "+s"(u) : "v"(after));
+    return (const SLAM_KARG A*)u;
+}
+// a struct of the argument segment (or of anywhere) as a plain value
+template <typename S, typename R>
+__device__ __forceinline__ S karg_copy(const R& r) {
+    S v;
+    __builtin_memcpy(&v, &r, sizeof(S));
+    return v;
+}
+
 template <typename S>
 __device__ __forceinline__ void st_wt_struct(S* dst, const S& v) {
     static_assert(sizeof(S) % 8 == 0, "8-byte granules");
@@ -569,9 +595,9 @@ __device__ void defer_epilogue(const int64_t base, const int64_t n, const double
         const int64_t i = base + kDeferPPT * t + k;
         if (i < bi) pre = fmax(pre, wv[k]);
         if (i == bi) {
-            dp.pxe[0][blk] = xv[k];
-            dp.pxe[1][blk] = yv[k];
-            dp.pxe[2][blk] = tv[k];
+            dp.pxe(0)[blk] = xv[k];
+            dp.pxe(1)[blk] = yv[k];
+            dp.pxe(2)[blk] = tv[k];
         }
     }
     pre = wave_max_f64(pre);
@@ -595,7 +621,7 @@ __device__ void defer_epilogue(const int64_t base, const int64_t n, const double
     if (t < kQ) {
         double acc = s_seg[16 * t];
         for (int mm = 1; mm < 16; ++mm) acc = acc + s_seg[16 * t + mm];
-        dp.ps[t][blk] = acc;
+        dp.ps(t)[blk] = acc;
     } else if (t >= 64 && t < 128) {
         // the block's np.sum subtree: its kLeaves leaves, then their pair sums
         // (wave 1; lane l < kLeaves holds leaf l)
@@ -609,11 +635,11 @@ __device__ void defer_epilogue(const int64_t base, const int64_t n, const double
             const double o = xor_f64(v, d);
             v = (lane & d) ? (o + v) : (v + o);
         }
-        if (t == 64) dp.leaf[blk] = v;
+        if (t == 64) dp.leaf()[blk] = v;
     } else if (t == 128) {
-        dp.pmax[blk] = M;
-        dp.pidx[blk] = bi;
-        dp.ppre[blk] = fmax(fmax(s_pre[0], s_pre[1]), fmax(s_pre[2], s_pre[3]));
+        dp.pmax()[blk] = M;
+        dp.pidx()[blk] = bi;
+        dp.ppre()[blk] = fmax(fmax(s_pre[0], s_pre[1]), fmax(s_pre[2], s_pre[3]));
     }
 }
 
@@ -1017,15 +1043,19 @@ __device__ SLAM_SLOW_ATTR double logsum_slow(const double xn, const double yn, c
 // the reference's (identical zero sets, <= 1e-12 relative).
 // Returns 1 when one of the lane's particles took the closed form's
 // double-double evaluation.
-template <int LIK, int P>
+// LC: LikConst, or the fused kernel's in its argument segment (kernarg_view),
+// whose words are then loaded where they are used; the helpers of the product
+// mode and of the slow path take a plain copy.
+template <int LIK, int P, typename LC>
 __device__ __forceinline__ int likelihood_lanes(const double* xn, const double* yn,
                                                  const double* sp, const double* cp,
                                                  const double* __restrict__ lm,
                                                  const double* __restrict__ z,
-                                                 const double* __restrict__ zc, const LikConst& lc,
+                                                 const double* __restrict__ zc, const LC& lc_in,
                                                  double* bn, const int wave_s, const double* pw) {
-    const int nl = lc.nl;
+    const int nl = lc_in.nl;
     if (LIK == SLAM_LIK_PRODUCT) {
+        const LikConst lc = karg_copy<LikConst>(lc_in);
         // the exp table in LDS, t.x halved for exp_nhalf (every lane of the
         // block reaches this barrier)
         __shared__ double2 s_etab[64];
@@ -1053,6 +1083,7 @@ __device__ __forceinline__ int likelihood_lanes(const double* xn, const double* 
         for (int k = 0; k < P; ++k) bn[k] = acc[k];
         return 0;
     }
+    const LC& lc = lc_in;
     double L[P];
     int lane_dd = 0;
     if (lc.closed) {
@@ -1137,6 +1168,9 @@ __device__ __forceinline__ int likelihood_lanes(const double* xn, const double* 
             L[k] = nl ? fma(-0.5, F * lc.rsx2, lc.neg_nl_ln_den) : lc.neg_nl_ln_den;
         }
         lane_dd = any_dd;
+        // (held as a lane value: as a lane mask it would occupy a scalar
+        // register pair across the exp and the slow path below)
+        asm("" : "+v"(lane_dd));
         if (any_dd) {
             const dd_t Sll{zc[0], zc[1]}, Slx{zc[2], zc[3]}, Sly{zc[4], zc[5]}, Szz{zc[6], zc[7]};
             const dd_t Szx{zc[8], zc[9]}, Szy{zc[10], zc[11]}, Dd{zc[12], zc[13]}, Ed{zc[14], zc[15]};
@@ -1233,12 +1267,15 @@ __device__ __forceinline__ int likelihood_lanes(const double* xn, const double* 
             atomicAdd(&g_probe_slow[1], 1ull);
         }
 #endif
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const double r = logsum_slow(__shfl(xn[k], l, 64), __shfl(yn[k], l, 64),
-                                         __shfl(sp[k], l, 64), __shfl(cp[k], l, 64), lm, z, lc);
-            if ((int)__lane_id() == l) bn[k] = r;
+        if (m) {
+            const LikConst lcs = karg_copy<LikConst>(lc);
+            do {
+                const int l = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const double r = logsum_slow(__shfl(xn[k], l, 64), __shfl(yn[k], l, 64),
+                                             __shfl(sp[k], l, 64), __shfl(cp[k], l, 64), lm, z, lcs);
+                if ((int)__lane_id() == l) bn[k] = r;
+            } while (m);
         }
     }
     return lane_dd;

@@ -1135,12 +1135,12 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
         has[2 * kp] = b < nb;
         has[2 * kp + 1] = b + 1 < nb;
         const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax + bb);
+        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
         pm[2 * kp] = t.x;
         pm[2 * kp + 1] = t.y;
 #pragma unroll
         for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps[j] + bb);
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
             q[2 * kp][j] = u.x;
             q[2 * kp + 1][j] = u.y;
         }
@@ -1149,7 +1149,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     double L[4];                                   // fused-block subtree sums
     {
         const int64_t c = tid / kFinLeafLanes;
-        const double* Lp = dp.leaf + 16 * (c < nfull ? c : 0) + 4 * part;
+        const double* Lp = dp.leaf() + 16 * (c < nfull ? c : 0) + 4 * part;
 #pragma unroll
         for (int j = 0; j < 4; ++j) L[j] = Lp[j];
     }
@@ -1158,7 +1158,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
 #pragma unroll
     for (int k = 0; k < kFinRegBlocks; ++k)
         if (has[k]) mlane = fmax(mlane, pm[k]);
-    for (int64_t b = bx0; b < nb; b += kFinThreads) mlane = fmax(mlane, dp.pmax[b]);
+    for (int64_t b = bx0; b < nb; b += kFinThreads) mlane = fmax(mlane, dp.pmax()[b]);
     // lane sums scaled by the lane's max; T = sum of w_un (unscaled)
     double acc[12];
 #pragma unroll
@@ -1181,8 +1181,8 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
         for (int64_t b = bx0; b < nb; b += kFinThreads) {
             double qq[11];
 #pragma unroll
-            for (int j = 0; j < 11; ++j) qq[j] = dp.ps[j][b];
-            add(dp.pmax[b], qq);
+            for (int j = 0; j < 11; ++j) qq[j] = dp.ps(j)[b];
+            add(dp.pmax()[b], qq);
         }
     }
     const double mx = wave_max_f64(mlane);
@@ -1193,7 +1193,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
         double v = 0.0;
         if (c < nfull) {
             if (c0 > 0) {
-                const double* Lp = dp.leaf + 16 * c + 4 * part;
+                const double* Lp = dp.leaf() + 16 * c + 4 * part;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) L[j] = Lp[j];
             }
@@ -1232,7 +1232,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
         for (int k = kFinRegBlocks - 1; k >= 0; --k)
             if (has[k] && pm[k] == M) mb = (unsigned long long)fin_blk(tid, k);
         for (int64_t b = bx0; b < nb && mb == ~0ull; b += kFinThreads)
-            if (dp.pmax[b] == M) mb = (unsigned long long)b;
+            if (dp.pmax()[b] == M) mb = (unsigned long long)b;
         if (mb != ~0ull) atomicMin(&s_mblk, mb);
     }
     PROBE_AT(1);
@@ -1246,7 +1246,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
                 if (has[k] && pm[k] >= thr && b >= prev) cb = b;
             }
             for (int64_t b = bx0; b < nb && cb == ~0ull; b += kFinThreads)
-                if ((unsigned long long)b >= prev && dp.pmax[b] >= thr) cb = (unsigned long long)b;
+                if ((unsigned long long)b >= prev && dp.pmax()[b] >= thr) cb = (unsigned long long)b;
         }
         if (cb != ~0ull) atomicMin(&s_cand[r], cb);
         __syncthreads();
@@ -1340,8 +1340,8 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
             }
         if (rec.idx < 0 && s_mblk != ~0ull) {
             const int64_t b = (int64_t)s_mblk;
-            rec.idx = gbase + dp.pidx[b];
-            for (int j = 0; j < 3; ++j) rec.xc[j] = dp.pxe[j][b];
+            rec.idx = gbase + dp.pidx()[b];
+            for (int j = 0; j < 3; ++j) rec.xc[j] = dp.pxe(j)[b];
         }
     }
     __syncthreads();
@@ -1503,7 +1503,7 @@ __device__ __forceinline__ void dist_finalize(const int64_t n, const DeferParts&
         const int64_t nb = (n + kPartPer - 1) / kPartPer;
         const int per = (int)((nb + kFinThreads - 1) / kFinThreads);
         const int64_t b0 = (int64_t)tid * per;
-        auto btot = [&](int64_t b) { return (dp.pmax[b] / s) * dp.ps[0][b]; };
+        auto btot = [&](int64_t b) { return (dp.pmax()[b] / s) * dp.ps(0)[b]; };
         double loc = 0.0;
         for (int k = 0; k < per; ++k)
             if (b0 + k < nb) loc += btot(b0 + k);

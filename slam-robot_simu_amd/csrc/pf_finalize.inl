@@ -47,10 +47,10 @@ struct FinRecord {
 };
 
 __device__ __forceinline__ void fin_load_record(const DeferParts& dp, const int64_t b, FinRecord& f) {
-    f.pre = dp.ppre[b];
-    f.pi = dp.pidx[b];
+    f.pre = dp.ppre()[b];
+    f.pi = dp.pidx()[b];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) f.xe[j] = dp.pxe[j][b];
+    for (int j = 0; j < 3; ++j) f.xe[j] = dp.pxe(j)[b];
 }
 
 // A lane of the np.sum pass takes 4 consecutive fused blocks of a buffer: each
@@ -145,12 +145,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_slices_kernel(const int6
         has[2 * kp] = b < nb;
         has[2 * kp + 1] = b + 1 < nb;
         const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax + bb);
+        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
         pm[2 * kp] = t.x;
         pm[2 * kp + 1] = t.y;
 #pragma unroll
         for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps[j] + bb);
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
             q[2 * kp][j] = u.x;
             q[2 * kp + 1][j] = u.y;
         }
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_slices_kernel(const int6
         const int64_t c = (int64_t)g * kFinBufPerRound + tid / kFinLeafLanes;
         double v = 0.0;
         if (c < nfull) {
-            const double* Lp = dp.leaf + 16 * c + 4 * part;
+            const double* Lp = dp.leaf() + 16 * c + 4 * part;
             v = (Lp[0] + Lp[1]) + (Lp[2] + Lp[3]);
         }
         {
@@ -351,7 +351,7 @@ __device__ void fin_next_prefix(const int64_t n, const int64_t nb, const bool ok
         __syncthreads();
         auto btot = [&](int64_t b) {
             if (in_lds) return sh[b];
-            if (ok) return (dp.pmax[b] / s) * dp.ps[0][b];
+            if (ok) return (dp.pmax()[b] / s) * dp.ps(0)[b];
             return btot_slow(b);
         };
         const int per = (int)((nb + kFinThreads - 1) / kFinThreads);
@@ -442,12 +442,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
         has[2 * kp] = b < nb;
         has[2 * kp + 1] = b + 1 < nb;
         const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax + bb);
+        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
         pm[2 * kp] = t.x;
         pm[2 * kp + 1] = t.y;
 #pragma unroll
         for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps[j] + bb);
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
             q[2 * kp][j] = u.x;
             q[2 * kp + 1][j] = u.y;
         }
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     const int part = tid & (kFinLeafLanes - 1);
     double L[4];                                   // fused-block subtree sums (buffer tid / 4 < nfull)
     {
-        const double* Lp = dp.leaf + 16 * (int64_t)(tid / kFinLeafLanes) + 4 * part;
+        const double* Lp = dp.leaf() + 16 * (int64_t)(tid / kFinLeafLanes) + 4 * part;
 #pragma unroll
         for (int j = 0; j < 4; ++j) L[j] = Lp[j];
     }
@@ -609,7 +609,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
 #pragma unroll
             for (int u = 0; u < kFinBatch; ++u) {
                 const int64_t b = b0 + (int64_t)u * kFinThreads;
-                v[u] = (b < nb) ? dp.pmax[b] : -1.0;
+                v[u] = (b < nb) ? dp.pmax()[b] : -1.0;
             }
 #pragma unroll
             for (int u = 0; u < kFinBatch; ++u) {
@@ -802,7 +802,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     double L[4];
     {
         const int64_t c = tid / kFinLeafLanes;
-        const double* Lp = dp.leaf + 16 * (c < nfull ? c : 0) + 4 * part;
+        const double* Lp = dp.leaf() + 16 * (c < nfull ? c : 0) + 4 * part;
 #pragma unroll
         for (int j = 0; j < 4; ++j) L[j] = Lp[j];
         __asm__ volatile("" ::: "memory");              // the leaves' loads issue first
@@ -815,7 +815,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         has[2 * kp] = b < nb;
         has[2 * kp + 1] = b + 1 < nb;
         const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax + bb);
+        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
         pm[2 * kp] = t.x;
         pm[2 * kp + 1] = t.y;
     }
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         const int64_t bb = b < nb ? b : 0;
 #pragma unroll
         for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps[j] + bb);
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
             q[2 * kp][j] = u.x;
             q[2 * kp + 1][j] = u.y;
         }
@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
 #pragma unroll
                     for (int k = 0; k < kFinRegBlocks; ++k) {
                         const int64_t b = (int64_t)g * kFinThreads * kFinRegBlocks + fin_blk(tid, k);
-                        v[k] = b < nb ? dp.pmax[b] : -1.0;
+                        v[k] = b < nb ? dp.pmax()[b] : -1.0;
                     }
 #pragma unroll
                     for (int k = kFinRegBlocks - 1; k >= 0; --k) {

@@ -49,14 +49,27 @@ constexpr int kPartPer = 256 * kDeferPPT;            // particles per fused bloc
 // Per block also: the largest w_un before the first max (-1 if none), so
 // the step end knows without a rescan whether a smaller weight can round to
 // the same normalised maximum, and the particle at the first max (x_est).
+// The 18 per-block arrays are one slab: array j starts at slab + j stride
+// (8-byte entries; stride a multiple of 16, so every array starts on a
+// 128-byte line, and at least blocks + 1: the step end loads entry pairs).
+// A kernel then carries one pointer and the stride for all of them, which
+// keeps the fused kernel's scalar registers free.
+constexpr int kDeferArrays = 18;    // pmax, pidx, ppre, pxe[3], ps[11], leaf (the last)
 struct DeferParts {
-    double* pmax;
-    int64_t* pidx;
-    double* ppre;           // max w_un at indices before pidx (-1: none)
-    double* pxe[3];         // particle (x, y, th) at pidx
-    double* ps[11];         // sw, sw2, m1[3], m2[6]
-    double* leaf;           // [blocks] the block's np.sum subtree (its kPartPer / 128 leaves, pairwise)
-    int64_t* mark;          // [npad] resample-run starts: (RNG step << 32) | source (expand pass)
+    double* slab;
+    int64_t stride;
+    __host__ __device__ double* arr(const int j) const { return slab + j * stride; }
+    __host__ __device__ double* pmax() const { return arr(0); }
+    __host__ __device__ int64_t* pidx() const { return reinterpret_cast<int64_t*>(arr(1)); }
+    // max w_un at indices before pidx (-1: none)
+    __host__ __device__ double* ppre() const { return arr(2); }
+    // particle (x, y, th) at pidx
+    __host__ __device__ double* pxe(const int j) const { return arr(3 + j); }
+    // sw, sw2, m1[3], m2[6]
+    __host__ __device__ double* ps(const int j) const { return arr(6 + j); }
+    // [blocks] the block's np.sum subtree (its kPartPer / 128 leaves, pairwise)
+    __host__ __device__ double* leaf() const { return arr(kDeferArrays - 1); }
+    int64_t* mark;         // [npad] resample-run starts: (RNG step << 32) | source (expand pass)
     int32_t* carry;         // [blocks] source of each fused block's first position
     // the resample gather reads source v at (x - goff)[v]: 0 on single-GPU
     // handles; npad on a sharded handle, whose particle arrays carry npad

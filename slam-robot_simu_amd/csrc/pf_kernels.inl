@@ -23,10 +23,37 @@ namespace slam {
 #else
 #define SLAM_FUSED_ATTR
 #endif
+// The fused kernel's argument segment, member for member SLAM_FUSED_PARAMS
+// (every member is 8-byte aligned and a multiple of 8 bytes long, so the
+// struct's layout is the segment's).  What the kernel needs only behind the
+// RNG and the likelihood -- the output pointers, flags, n, refp, the block
+// partials' slab -- it reads from here at that point (kernarg_view), and the
+// likelihood its constants, so that no scalar register holds them from the
+// kernel's start.
+struct FusedArgs {
+    int64_t n;
+    const double *xs, *ys, *ts;
+    double *xo, *yo, *to, *w_un;
+    const double* c;
+    int32_t* flags;
+    const double *noise, *lm;
+    StepIO io;
+    PredictConst pc;
+    LikConst lc;
+    uint64_t seed;
+    const double *s_in, *refp;
+    DeferParts dp;
+};
+static_assert(sizeof(StepIO) % 8 == 0 && sizeof(PredictConst) % 8 == 0 && sizeof(LikConst) % 8 == 0 &&
+                  sizeof(DeferParts) % 8 == 0 && alignof(FusedArgs) == 8,
+              "FusedArgs is the argument segment's layout");
+
 // One fused block's tile (blk: 256 lanes x P particles): the body of
 // pf_fused_kernel (a persistent grid walking tiles measured slower: DESIGN 4.4).
+// Returns the lane's first new weight (what follows the tile anchors its own
+// kernarg_view on it).
 template <int MOTION, int LIK, bool HOSTNOISE, bool WT>
-__device__ __forceinline__ void pf_fused_tile(
+__device__ __forceinline__ double pf_fused_tile(
     const int64_t blk, const int32_t st, const uint32_t rstep, const int32_t rflag,
     const double* __restrict__ zs, const int wave_s, const RngTabs& rtab,
     const int64_t n, const double* __restrict__ xs, const double* __restrict__ ys,
@@ -253,28 +280,60 @@ __device__ __forceinline__ void pf_fused_tile(
     for (int k = 0; k < P; ++k) bn[k] = exp_lean(-1e-3 * (xv[k] + yv[k] + sp[k] + cp[k]));
     const int lane_dd = 0;
 #else
-    const int lane_dd = likelihood_lanes<LIK, P>(xv, yv, sp, cp, lm, zs,
-                                                 io.zc + (size_t)st * kZcWords, lc, bn, wave_s, pw);
+    int lane_dd;
+    if constexpr (LIK == SLAM_LIK_PRODUCT) {
+        lane_dd = likelihood_lanes<LIK, P>(xv, yv, sp, cp, lm, zs, io.zc + (size_t)st * kZcWords,
+                                           lc, bn, wave_s, pw);
+    } else {
+        // the likelihood's constants from the argument segment, word by word
+        // where the closed form uses them.  (The pointers it loads through
+        // stay the kernel's own parameters: a pointer read from the segment
+        // is not known to be unaliased, and the loads through it would be
+        // per-lane ones.)
+        const SLAM_KARG FusedArgs* km = kernarg_view<FusedArgs>(xv[0]);
+        lane_dd = likelihood_lanes<LIK, P>(xv, yv, sp, cp, lm, zs, io.zc + (size_t)st * kZcWords,
+                                           km->lc, bn, wave_s, pw);
+    }
 #endif
     FPROBE(4, bn[P - 1]);
-    if (__ballot(lane_dd) != 0 && __lane_id() == 0) atomicAdd(&flags[kFlagDDWaves], 1);
+    // ---- the step's outputs.  Everything from here on takes its arguments
+    //      from the argument segment (ka) and forms the block's base and the
+    //      lanes' validity again (b2: the block index, which is blk, behind an
+    //      empty asm, or the compiler keeps the values of the kernel's start),
+    //      so that none of them is held across the RNG and the likelihood
+    const SLAM_KARG FusedArgs* ka = kernarg_view<FusedArgs>(bn[0]);
+    int32_t* const flags_l = ka->flags;
+    if (__ballot(lane_dd) != 0 && __lane_id() == 0) atomicAdd(&flags_l[kFlagDDWaves], 1);
+    uint32_t b2 = blockIdx.x;
+    asm("" : "+s"(b2) : "v"(bn[0]));
+    const int64_t n_l = ka->n;
+    const int64_t base_l = (int64_t)b2 * (256 * P);
+    const int64_t i0_l = base_l + P * (((int64_t)wave_s << 6) | (int64_t)__lane_id());
     double wv[P];
 #pragma unroll
-    for (int k = 0; k < P; ++k) wv[k] = valid[k] ? pw[k] * bn[k] : 0.0;   // particle_filter.py:194
+    for (int k = 0; k < P; ++k) wv[k] = i0_l + k < n_l ? pw[k] * bn[k] : 0.0;   // particle_filter.py:194
     if constexpr (kLate) {
+        double* const xo_l = ka->xo;
+        double* const yo_l = ka->yo;
+        double* const to_l = ka->to;
 #pragma unroll
         for (int h = 0; h < P; h += 2) {
-            st_pair(xo + i0 + h, xv[h], xv[h + 1]);
-            st_pair(yo + i0 + h, yv[h], yv[h + 1]);
-            st_pair(to + i0 + h, tv[h], tv[h + 1]);
+            st_pair(xo_l + i0_l + h, xv[h], xv[h + 1]);
+            st_pair(yo_l + i0_l + h, yv[h], yv[h + 1]);
+            st_pair(to_l + i0_l + h, tv[h], tv[h + 1]);
         }
     }
+    double* const w_un_l = ka->w_un;
 #pragma unroll
-    for (int h = 0; h < P; h += 2) st_pair(w_un + i0 + h, wv[h], wv[h + 1]);
+    for (int h = 0; h < P; h += 2) st_pair(w_un_l + i0_l + h, wv[h], wv[h + 1]);
 #ifndef SLAM_NO_EPILOGUE
-    defer_epilogue(base, n, wv, xv, yv, tv, refp, dp, wave_s, (int)blk);
+    DeferParts dpl{};
+    dpl.slab = ka->dp.slab;
+    dpl.stride = ka->dp.stride;
+    defer_epilogue(base_l, n_l, wv, xv, yv, tv, ka->refp, dpl, wave_s, (int)b2);
 #endif
     FPROBE(5, wv[0]);
+    return wv[0];
 }
 
 // The step's first fused block, after its own particles: the NEXT step's
@@ -283,12 +342,19 @@ __device__ __forceinline__ void pf_fused_tile(
 // moved twice.  Off the step's critical path: the next launch reads them; a
 // step staged by the host is prepared again by its prestep.
 template <int MOTION>
-__device__ __forceinline__ void pf_fused_prep_next(const int32_t st, const int wave_s,
-                                                   const double* __restrict__ lm,
-                                                   const StepIO& io, const PredictConst& pc,
-                                                   const LikConst& lc,
-                                                   const double* __restrict__ refp) {
-    if (MOTION != kMotionNone && lc.closed && blockIdx.x == 0 && st + 1 < io.cap) {
+__device__ __forceinline__ void pf_fused_prep_next(const int wave_s, const double after) {
+    if (MOTION == kMotionNone || blockIdx.x != 0) return;
+    // (its arguments from the argument segment, as the tile's outputs, and
+    // the step index read again: the step end advances it, after this launch)
+    const SLAM_KARG FusedArgs* ka = kernarg_view<FusedArgs>(after);
+    if (!ka->lc.closed) return;
+    const int32_t st = __builtin_amdgcn_readfirstlane(ka->io.ctr[0]);
+    if (st + 1 < ka->io.cap) {
+        const StepIO io = karg_copy<StepIO>(ka->io);
+        const PredictConst pc = karg_copy<PredictConst>(ka->pc);
+        const LikConst lc = karg_copy<LikConst>(ka->lc);
+        const double* __restrict__ lm = ka->lm;
+        const double* __restrict__ refp = ka->refp;
         __shared__ double s_prep[16];
         const int32_t sn = st + 1;
         closed_prep_sums(lm, io.z + (size_t)sn * 2 * lc.nl, lc.nl, wave_s, 4, s_prep);
@@ -332,9 +398,9 @@ template <int MOTION, int LIK, bool HOSTNOISE, bool WT>
 __global__ __launch_bounds__(256) SLAM_FUSED_ATTR void pf_fused_kernel(SLAM_FUSED_PARAMS) {
     static_assert(kDeferPPT % 2 == 0, "the fused kernel moves particle pairs");
     SLAM_FUSED_PROLOGUE
-    pf_fused_tile<MOTION, LIK, HOSTNOISE, WT>(blockIdx.x, st, rstep, rflag, zs, wave_s, rtab,
-                                              SLAM_FUSED_ARGS);
-    pf_fused_prep_next<MOTION>(st, wave_s, lm, io, pc, lc, refp);
+    const double w0 = pf_fused_tile<MOTION, LIK, HOSTNOISE, WT>(blockIdx.x, st, rstep, rflag, zs,
+                                                                wave_s, rtab, SLAM_FUSED_ARGS);
+    pf_fused_prep_next<MOTION>(wave_s, w0);
 }
 
 // ====================================================================
