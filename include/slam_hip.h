@@ -433,6 +433,82 @@ typedef struct {
 
 int slam_ekfslam_info(slam_ekfslam* h, slam_ekfslam_info_t* out);
 
+/* --------------------------------------------------------------------
+ * EKF-SLAM without ids: maximum-likelihood association, landmark
+ * initialisation, a map that grows from nothing (the rule is the
+ * one of the associating FastSLAM handles below).
+ *
+ * An associating handle has a capacity cap (n = 3 + 3 cap) and holds
+ * count <= cap landmarks in slots 0..count-1, in creation order; nothing is
+ * removed.  Rows and columns of P and entries of mu at or beyond
+ * n_act = 3 + 3 count are exactly zero and stay so.
+ *
+ * slam_ekfslam_observe(h, k, obs, assoc_out) takes 0 <= k <= 40 observations
+ * (range, bearing, orientation) without identity.  count0 is the count at
+ * entry; every score uses the state at entry (the predicted state).
+ *  1. Score.  For each observation t in turn and each slot j < count0 not yet
+ *     matched in this call: l_tj = -(e^T S^-1 e + ln det S) / 2 - (3/2) ln 2 pi
+ *     with e the wrapped innovation of the ScanSensor model and
+ *     S = [Hr Hl] P[{r,j},{r,j}] [Hr Hl]^T + R(obs_t[0]) (3 x 3, from the 6 x 6
+ *     block of P over the robot and slot j; Hr, Hl, R as in the update).
+ *  2. Choose.  The largest score wins, the lowest slot on a tie, a NaN score
+ *     never.  Without a candidate, or with l_best < log_p_new, the observation
+ *     is new (assoc_out[t] = -1), or dropped when no slot is left (-2).
+ *     Otherwise it is matched to that slot (assoc_out[t] = slot), which is then
+ *     excluded for the rest of the call.  A slot created in this call is never
+ *     a candidate.
+ *  3. Update.  The matched observations, in observation order, make one batched
+ *     update: slam_ekfslam_update's arithmetic with those slots as ids, over
+ *     the active prefix only.  No match, no update.
+ *  4. Initialise.  Each new observation, in observation order, from the
+ *     posterior mu_r, P of step 3, into slot s = count (count then grows by
+ *     one).  With psi = pi/2 - yaw, c = cos psi, s = sin psi, rx = d cos b,
+ *     ry = d sin b, dx = c rx + s ry, dy = -s rx + c ry:
+ *       mu_s = (x + dx, y + dy, wrap(o - psi)),
+ *       G_r = [[1, 0, -dy], [0, 1, dx], [0, 0, 1]],
+ *       G_z = [[dx/d, -dy, 0], [dy/d, dx, 0], [0, 0, 1]],
+ *       P_s,i = G_r P_r,i for every column i < 3 + 3 s (landmarks initialised
+ *       earlier in the same call included), P_ss = G_r P_rr G_r^T + G_z R G_z^T.
+ * obs must be finite and the ranges positive, else SLAM_ERR_ARG before any HIP
+ * call (slam_ekfslam_check_observations is that check alone, host only).
+ * slam_ekfslam_predict touches the active rows only; slam_ekfslam_update on an
+ * associating handle checks its ids against count and walks the prefix too.
+ * -------------------------------------------------------------------- */
+typedef struct {
+    double log_p_new;     /* ln of the likelihood below which an observation starts a landmark */
+    int32_t record;       /* keep the last call's scores for slam_ekfslam_get_scores */
+    int32_t pad;
+} slam_ekfslam_assoc_config;
+
+int slam_ekfslam_create_assoc(const slam_ekfslam_config* cfg, const slam_ekfslam_assoc_config* acfg,
+                              int64_t capacity, int device, slam_ekfslam** out);
+int slam_ekfslam_check_observations(int32_t k, const double* obs);
+/* assoc_out (k entries: slot, -1 new, -2 dropped) may be NULL. */
+int slam_ekfslam_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_out);
+/* slam_ekfslam_predict followed by slam_ekfslam_observe. */
+int slam_ekfslam_step_assoc(slam_ekfslam* h, const double* control, int32_t k, const double* obs,
+                            int32_t* assoc_out);
+int slam_ekfslam_get_count(slam_ekfslam* h, int32_t* count);
+/* For placing a state (slam_ekfslam_set_state): the caller keeps the zero tail. */
+int slam_ekfslam_set_count(slam_ekfslam* h, int32_t count);
+/* The last observe's k x count0 scores (record set), row-major. */
+int slam_ekfslam_get_scores(slam_ekfslam* h, double* out);
+
+typedef struct {
+    int64_t n_act;        /* 3 + 3 count */
+    int64_t tiles;        /* 128 x 128 tiles the last observe's update walked (0: no update) */
+    int32_t count;
+    int32_t count0;       /* count at the last observe's entry */
+    int32_t matched;      /* of the last observe */
+    int32_t created;
+    int32_t dropped;
+    int32_t pad0;
+} slam_ekfslam_assoc_info_t;
+
+int slam_ekfslam_assoc_info(slam_ekfslam* h, slam_ekfslam_assoc_info_t* out);
+/* Device time of the last observe (ms): out[4] = {scan, assign, update, initialise}. */
+int slam_ekfslam_assoc_timing(slam_ekfslam* h, double* out);
+
 /* ====================================================================
  * FastSLAM 1.0 with known data association (an extension: the reference's
  * particle filter localises against a known map); per-particle

@@ -12,6 +12,7 @@
 
 #include "device_mem.hpp"
 #include "ekf_kernels.inl"
+#include "ekf_assoc.inl"
 
 using namespace slam;
 
@@ -58,6 +59,21 @@ struct slam_ekfslam {
     int32_t last_m = 0;            // slam_ekfslam_info: the last update's operand width
     int32_t last_rank = SLAM_EKS_RANK_NONE;     // ... and the kernels it launched
     int32_t last_apply = SLAM_EKS_APPLY_NONE;
+    // associating handle (slam_ekfslam_create_assoc): n_lm is the capacity
+    bool assoc = false;
+    slam_ekfslam_assoc_config acfg{};
+    int32_t count = 0;             // landmarks held: slots 0..count-1
+    double* scores = nullptr;      // [kEksMaxObs][n_lm]
+    int32_t* taken = nullptr;      // n_lm
+    int32_t* res = nullptr;        // {matched, new count, assoc[kEksMaxObs]}
+    hipEvent_t aev[5] = {};
+    double assoc_ms[4] = {0, 0, 0, 0};
+    int32_t last_k = 0, last_count0 = 0;
+    int32_t last_matched = 0, last_new = 0, last_dropped = 0;
+    int64_t last_tiles = 0;        // tiles the last update walked
+
+    // rows of the state in use: all of it, or an associating handle's prefix
+    int64_t n_act() const { return assoc ? 3 + 3 * (int64_t)count : n; }
 };
 
 namespace {
@@ -120,6 +136,10 @@ int ekf_launch(slam_ekf* h, int32_t steps, const double* control, double* xm_las
 }
 
 // ---------------------------------------------------------------- EKF-SLAM
+// acfg: NULL for a known-id handle
+int eks_create(const slam_ekfslam_config* cfg, const slam_ekfslam_assoc_config* acfg,
+               int64_t n_landmarks, int device, slam_ekfslam** out);
+
 EksConst eks_const(const slam_ekfslam_config& c) {
     EksConst k;
     k.dt = c.dt;
@@ -134,10 +154,10 @@ EksConst eks_const(const slam_ekfslam_config& c) {
 
 int eks_predict(slam_ekfslam* h, const double* control) {
     const double v = control[0], om = control[1];
-    const int64_t rows = h->n - 3;
+    const int64_t n = h->n_act(), rows = n - 3;
     if (rows > 0)
         hipLaunchKernelGGL(eks_predict_rows_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256),
-                           0, h->stream, h->P, h->n, h->ld, h->mu, eks_const(h->cfg), v, om);
+                           0, h->stream, h->P, n, h->ld, h->mu, eks_const(h->cfg), v, om);
     hipLaunchKernelGGL(eks_predict_pose_kernel, dim3(1), dim3(64), 0, h->stream, h->P, h->ld,
                        h->mu, eks_const(h->cfg), v, om);
     SLAM_HIP_TRY(hipGetLastError());
@@ -147,7 +167,12 @@ int eks_predict(slam_ekfslam* h, const double* control) {
 int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs) {
     SLAM_ARG_CHECK(k >= 1 && 3 * k <= kEksMaxM, "slam_ekfslam_update: need 1 <= k <= 40");
     for (int32_t t = 0; t < k; ++t)
-        SLAM_ARG_CHECK(ids[t] >= 0 && ids[t] < h->n_lm, "slam_ekfslam_update: landmark id out of range");
+        SLAM_ARG_CHECK(ids[t] >= 0 && ids[t] < (h->assoc ? h->count : h->n_lm),
+                       "slam_ekfslam_update: landmark id out of range");
+    // the rows the kernels walk: the whole state, or an associating handle's
+    // active prefix and its own 128-row round-up (the rest of P is zero)
+    const int64_t n = h->n_act();
+    const int64_t n_pad = h->assoc ? (n + kEksTile - 1) / kEksTile * kEksTile : h->n_pad;
     const int32_t m = 3 * k;
     const int32_t M = (m + 3) / 4 * 4;
     h->last_m = M;
@@ -158,37 +183,38 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
     SLAM_HIP_TRY(hipEventRecord(h->ev[0], h->stream));
     hipLaunchKernelGGL(eks_build_kernel, dim3(1), dim3(128), 0, h->stream, h->mu, ob, h->ids, k,
                        M, c, h->hs, h->e, h->rd);
-    hipLaunchKernelGGL(eks_pht_kernel, dim3((unsigned)((h->n_pad + 255) / 256)), dim3(256), 0,
-                       h->stream, h->P, h->n, h->ld, h->n_pad, h->ids, h->hs, k, M, h->pht);
+    hipLaunchKernelGGL(eks_pht_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0,
+                       h->stream, h->P, n, h->ld, n_pad, h->ids, h->hs, k, M, h->pht);
     SLAM_HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     const size_t sbytes = (size_t)M * M * sizeof(double);
     hipLaunchKernelGGL(eks_gain_kernel, dim3(1), dim3(1024), sbytes, h->stream, h->pht, h->ids,
                        h->hs, h->rd, k, M, h->sinv);
     SLAM_HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    const int64_t apply_grid = std::min<int64_t>(512, (h->n_pad + 15) / 16);
+    const int64_t apply_grid = std::min<int64_t>(512, (n_pad + 15) / 16);
     if (M <= 64 && !h->apply_lds) {
-        hipLaunchKernelGGL(eks_apply_mfma_kernel, dim3((unsigned)((h->n_pad / 16 + 3) / 4)), dim3(256),
-                           0, h->stream, h->pht, h->sinv, h->e, h->n, h->n_pad, M, h->kg, h->mu);
+        hipLaunchKernelGGL(eks_apply_mfma_kernel, dim3((unsigned)((n_pad / 16 + 3) / 4)), dim3(256),
+                           0, h->stream, h->pht, h->sinv, h->e, n, n_pad, M, h->kg, h->mu);
         h->last_apply = SLAM_EKS_APPLY_MFMA;
     } else {
         hipLaunchKernelGGL(eks_apply_kernel, dim3((unsigned)apply_grid), dim3(kEksApplyThreads),
-                           sbytes, h->stream, h->pht, h->sinv, h->e, h->n, h->n_pad, M, h->kg, h->mu);
+                           sbytes, h->stream, h->pht, h->sinv, h->e, n, n_pad, M, h->kg, h->mu);
         h->last_apply = SLAM_EKS_APPLY_LDS;
     }
     SLAM_HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-    const int64_t nt = h->n_pad / kEksTile;
+    const int64_t nt = n_pad / kEksTile;
     const int64_t tiles = nt * (nt + 1) / 2;
+    h->last_tiles = tiles;
 #ifndef SLAM_EKS_PIPE
 #define SLAM_EKS_PIPE 1
 #endif
     if (h->frag_grid > 0 && M <= kEksPipeK && h->kernel_sel == 0) {
-        const int64_t tot = h->n_pad * M;
+        const int64_t tot = n_pad * M;
         hipLaunchKernelGGL(eks_frag_layout_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0,
-                           h->stream, h->kg, h->pht, h->n_pad, M, h->kf, h->hf);
+                           h->stream, h->kg, h->pht, n_pad, M, h->kf, h->hf);
 #define SLAM_EKS_FRAG_S(QQ, WM, WN)                                                               \
     hipLaunchKernelGGL((eks_rank_update_frag_kernel<QQ, WM, WN>), dim3((unsigned)h->frag_grid),   \
-                       dim3(EksFragShape<WM, WN>::kThreads), 0, h->stream, h->P, h->n, h->ld,      \
-                       h->kf, h->hf, h->n_pad, tiles)
+                       dim3(EksFragShape<WM, WN>::kThreads), 0, h->stream, h->P, n, h->ld,         \
+                       h->kf, h->hf, n_pad, tiles)
 #define SLAM_EKS_FRAG(QQ)                                                                         \
     case QQ:                                                                                      \
         if (h->frag_shape == 1) {                                                                 \
@@ -201,8 +227,8 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
         break
 #define SLAM_EKS_FRAG_P(QQ, PF)                                                                   \
     hipLaunchKernelGGL((eks_rank_update_frag_kernel<QQ, 2, 4, PF>), dim3((unsigned)h->frag_grid), \
-                       dim3(EksFragShape<2, 4>::kThreads), 0, h->stream, h->P, h->n, h->ld,        \
-                       h->kf, h->hf, h->n_pad, tiles)
+                       dim3(EksFragShape<2, 4>::kThreads), 0, h->stream, h->P, n, h->ld,           \
+                       h->kf, h->hf, n_pad, tiles)
         if (M / 4 == 15 && h->frag_pf == 1) {
             SLAM_EKS_FRAG_P(15, 7);
             h->last_rank = SLAM_EKS_RANK_FRAG_2X4_PF;
@@ -221,13 +247,13 @@ int eks_update(slam_ekfslam* h, int32_t k, const int64_t* ids, const double* obs
 #undef SLAM_EKS_FRAG
     } else if (SLAM_EKS_PIPE && h->pipe_grid > 0 && M <= kEksPipeK) {
         hipLaunchKernelGGL(eks_rank_update_pipelined_kernel, dim3((unsigned)h->pipe_grid),
-                           dim3(kEksPipeThreads), 0, h->stream, h->P, h->n, h->ld, h->kg, h->pht, M,
+                           dim3(kEksPipeThreads), 0, h->stream, h->P, n, h->ld, h->kg, h->pht, M,
                            tiles);
         h->last_rank = SLAM_EKS_RANK_PIPE;
     } else {
         const int64_t grid = (tiles + 7) / 8 * 8;
         hipLaunchKernelGGL(eks_rank_update_kernel, dim3((unsigned)grid), dim3(kEksThreads), 0,
-                           h->stream, h->P, h->n, h->ld, h->kg, h->pht, M, tiles);
+                           h->stream, h->P, n, h->ld, h->kg, h->pht, M, tiles);
         h->last_rank = SLAM_EKS_RANK_LDS;
     }
     SLAM_HIP_TRY(hipEventRecord(h->ev[4], h->stream));
@@ -395,6 +421,26 @@ int slam_ekf_synchronize(slam_ekf* h) {
 int slam_ekfslam_create(const slam_ekfslam_config* cfg, int64_t n_landmarks, int device,
                         slam_ekfslam** out) {
     SLAM_ARG_CHECK(cfg && out && n_landmarks >= 1, "slam_ekfslam_create: bad arguments");
+    return eks_create(cfg, nullptr, n_landmarks, device, out);
+}
+
+int slam_ekfslam_create_assoc(const slam_ekfslam_config* cfg, const slam_ekfslam_assoc_config* acfg,
+                              int64_t capacity, int device, slam_ekfslam** out) {
+    SLAM_ARG_CHECK(cfg && acfg && out, "slam_ekfslam_create_assoc: NULL argument");
+    *out = nullptr;
+    SLAM_ARG_CHECK(capacity >= 1 && capacity <= (int64_t)1 << 24,
+                   "slam_ekfslam_create_assoc: capacity must be in 1..2^24");
+    SLAM_ARG_CHECK(std::isfinite(acfg->log_p_new),
+                   "slam_ekfslam_create_assoc: log_p_new must be finite");
+    return eks_create(cfg, acfg, capacity, device, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int eks_create(const slam_ekfslam_config* cfg, const slam_ekfslam_assoc_config* acfg,
+               int64_t n_landmarks, int device, slam_ekfslam** out) {
     SLAM_ARG_CHECK(cfg->motion == SLAM_MOTION_LINEAR || cfg->motion == SLAM_MOTION_VELOCITY,
                    "slam_ekfslam_create: bad motion model");
     *out = nullptr;
@@ -464,7 +510,196 @@ int slam_ekfslam_create(const slam_ekfslam_config* cfg, int64_t n_landmarks, int
         hipFuncSetAttribute((const void*)eks_apply_kernel,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)big) != hipSuccess)
         return fail(SLAM_ERR_HIP, "slam_ekfslam_create: LDS attribute failed");
+    if (acfg) {
+        h->assoc = true;
+        h->acfg = *acfg;
+        if (m.alloc(&h->scores, (size_t)kEksMaxObs * n_landmarks) ||
+            m.alloc(&h->taken, (size_t)n_landmarks) || m.alloc(&h->res, 2 + kEksMaxObs))
+            return fail(SLAM_ERR_HIP, "slam_ekfslam_create_assoc: allocation failed");
+        for (auto& e : h->aev)
+            if (m.event(&e))
+                return fail(SLAM_ERR_HIP, "slam_ekfslam_create_assoc: event creation failed");
+    }
     *out = hp.release();
+    return SLAM_OK;
+}
+
+// k observations without ids: finite, range > 0 (host only)
+int eks_check_observations(const char* who, int32_t k, const double* obs) {
+    SLAM_ARG_CHECK(k >= 0 && k <= kEksMaxObs, std::string(who) + ": need 0 <= k <= 40");
+    SLAM_ARG_CHECK(k == 0 || obs, std::string(who) + ": NULL observations");
+    for (int32_t u = 0; u < 3 * k; ++u)
+        SLAM_ARG_CHECK(std::isfinite(obs[u]), std::string(who) + ": observations must be finite");
+    for (int32_t t = 0; t < k; ++t)
+        SLAM_ARG_CHECK(obs[3 * t] > 0.0, std::string(who) + ": ranges must be positive");
+    return SLAM_OK;
+}
+
+// Score, choose, update over the active prefix, initialise (include/slam_hip.h).
+int eks_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_out) {
+    const EksConst c = eks_const(h->cfg);
+    const int32_t count0 = h->count;
+    const int64_t cap = h->n_lm;
+    h->last_k = k;
+    h->last_count0 = count0;
+    h->last_matched = h->last_new = h->last_dropped = 0;
+    h->last_tiles = 0;
+    for (double& v : h->assoc_ms) v = 0.0;
+    if (k == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipEventRecord(h->aev[0], h->stream));
+    if (count0 > 0) {
+        EksScan sc{};
+        for (int32_t u = 0; u < 3 * k; ++u) sc.obs[u] = obs[u];
+        hipLaunchKernelGGL(eks_scan_kernel,
+                           dim3((unsigned)((count0 + kEksScanThreads - 1) / kEksScanThreads)),
+                           dim3(kEksScanThreads), 0, h->stream, h->P, h->ld, h->mu, count0, k, sc, c,
+                           cap, h->scores);
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->aev[1], h->stream));
+    hipLaunchKernelGGL(eks_assign_kernel, dim3(1), dim3(kEksAssignThreads), 0, h->stream, h->scores,
+                       cap, count0, (int32_t)cap, k, h->acfg.log_p_new, h->taken, h->res);
+    SLAM_HIP_TRY(hipEventRecord(h->aev[2], h->stream));
+    SLAM_HIP_TRY(hipGetLastError());
+    int32_t res[2 + kEksMaxObs];
+    SLAM_HIP_TRY(hipMemcpyAsync(res, h->res, (2 + k) * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    // the matched and the new observations, each in observation order: the
+    // update and the initialisation take them in their kernel arguments
+    int64_t ids[kEksMaxObs];
+    double mobs[3 * kEksMaxObs];
+    EksNew nw{};
+    int32_t nm = 0;
+    for (int32_t t = 0; t < k; ++t) {
+        const int32_t a = res[2 + t];
+        if (assoc_out) assoc_out[t] = a;
+        if (a >= 0) {
+            ids[nm] = a;
+            for (int q = 0; q < 3; ++q) mobs[3 * nm + q] = obs[3 * t + q];
+            ++nm;
+        } else if (a == -1) {
+            for (int q = 0; q < 3; ++q) nw.obs[3 * nw.n_new + q] = obs[3 * t + q];
+            ++nw.n_new;
+        } else {
+            ++h->last_dropped;
+        }
+    }
+    if (nm != res[0] || count0 + nw.n_new != res[1] || res[1] > cap)
+        return fail(SLAM_ERR_STATE, "slam_ekfslam_observe: inconsistent assignment");
+    h->last_matched = nm;
+    h->last_new = nw.n_new;
+    if (nm > 0) {
+        int rc = eks_update(h, nm, ids, mobs);
+        if (rc) return rc;
+    }
+    if (nw.n_new > 0) {
+        SLAM_HIP_TRY(hipEventRecord(h->aev[3], h->stream));
+        const int64_t cols = 3 + 3 * (int64_t)(count0 + nw.n_new);
+        hipLaunchKernelGGL(eks_init_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)nw.n_new),
+                           dim3(256), 0, h->stream, h->P, h->ld, h->mu, count0, nw, c);
+        SLAM_HIP_TRY(hipEventRecord(h->aev[4], h->stream));
+        SLAM_HIP_TRY(hipGetLastError());
+        h->count = count0 + nw.n_new;
+    }
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    float ms;
+    SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->aev[0], h->aev[1]));
+    h->assoc_ms[0] = ms;
+    SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->aev[1], h->aev[2]));
+    h->assoc_ms[1] = ms;
+    if (nm > 0) {
+        int rc = eks_collect_timing(h);
+        if (rc) return rc;
+        h->assoc_ms[2] = h->last_ms[0] + h->last_ms[1] + h->last_ms[2] + h->last_ms[3];
+    }
+    if (nw.n_new > 0) {
+        SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->aev[3], h->aev[4]));
+        h->assoc_ms[3] = ms;
+    }
+    return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slam_ekfslam_check_observations(int32_t k, const double* obs) {
+    return eks_check_observations("slam_ekfslam_check_observations", k, obs);
+}
+
+int slam_ekfslam_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_out) {
+    SLAM_ARG_CHECK(h, "slam_ekfslam_observe: NULL handle");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_observe: not an associating handle");
+    int rc = eks_check_observations("slam_ekfslam_observe", k, obs);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    return eks_observe(h, k, obs, assoc_out);
+}
+
+int slam_ekfslam_step_assoc(slam_ekfslam* h, const double* control, int32_t k, const double* obs,
+                            int32_t* assoc_out) {
+    SLAM_ARG_CHECK(h && control, "slam_ekfslam_step_assoc: NULL argument");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_step_assoc: not an associating handle");
+    int rc = eks_check_observations("slam_ekfslam_step_assoc", k, obs);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    rc = eks_predict(h, control);
+    if (rc) return rc;
+    rc = eks_observe(h, k, obs, assoc_out);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+int slam_ekfslam_get_count(slam_ekfslam* h, int32_t* count) {
+    SLAM_ARG_CHECK(h && count, "slam_ekfslam_get_count: NULL argument");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_get_count: not an associating handle");
+    *count = h->count;
+    return SLAM_OK;
+}
+
+int slam_ekfslam_set_count(slam_ekfslam* h, int32_t count) {
+    SLAM_ARG_CHECK(h, "slam_ekfslam_set_count: NULL handle");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_set_count: not an associating handle");
+    SLAM_ARG_CHECK(count >= 0 && count <= h->n_lm, "slam_ekfslam_set_count: need 0 <= count <= capacity");
+    h->count = count;
+    return SLAM_OK;
+}
+
+int slam_ekfslam_get_scores(slam_ekfslam* h, double* out) {
+    SLAM_ARG_CHECK(h && out, "slam_ekfslam_get_scores: NULL argument");
+    SLAM_ARG_CHECK(h->assoc && h->acfg.record,
+                   "slam_ekfslam_get_scores: the handle was not created with record set");
+    if (h->last_k == 0 || h->last_count0 == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    const size_t w = (size_t)h->last_count0 * sizeof(double);
+    SLAM_HIP_TRY(hipMemcpy2DAsync(out, w, h->scores, (size_t)h->n_lm * sizeof(double), w, h->last_k,
+                                  hipMemcpyDeviceToHost, h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+static_assert(sizeof(slam_ekfslam_assoc_info_t) == 40,
+              "slamhip/_lib.py EKFSLAMAssocInfo mirrors this layout");
+
+int slam_ekfslam_assoc_info(slam_ekfslam* h, slam_ekfslam_assoc_info_t* out) {
+    SLAM_ARG_CHECK(h && out, "slam_ekfslam_assoc_info: NULL argument");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_assoc_info: not an associating handle");
+    *out = slam_ekfslam_assoc_info_t{};
+    out->n_act = h->n_act();
+    out->tiles = h->last_tiles;
+    out->count = h->count;
+    out->count0 = h->last_count0;
+    out->matched = h->last_matched;
+    out->created = h->last_new;
+    out->dropped = h->last_dropped;
+    return SLAM_OK;
+}
+
+int slam_ekfslam_assoc_timing(slam_ekfslam* h, double* out) {
+    SLAM_ARG_CHECK(h && out, "slam_ekfslam_assoc_timing: NULL argument");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_assoc_timing: not an associating handle");
+    for (int q = 0; q < 4; ++q) out[q] = h->assoc_ms[q];
     return SLAM_OK;
 }
 

@@ -63,6 +63,19 @@ EKS_RANK = {0: None, 1: "frag2x4", 2: "frag2x2", 3: "frag2x4_pf", 4: "pipe", 5: 
 EKS_APPLY = {0: None, 1: "mfma", 2: "lds"}
 
 
+class EKFSLAMAssocConfig(C.Structure):
+    _fields_ = [("log_p_new", C.c_double), ("record", C.c_int32), ("pad", C.c_int32)]
+
+
+class EKFSLAMAssocInfo(C.Structure):
+    _fields_ = [("n_act", C.c_int64), ("tiles", C.c_int64), ("count", C.c_int32),
+                ("count0", C.c_int32), ("matched", C.c_int32), ("created", C.c_int32),
+                ("dropped", C.c_int32), ("pad0", C.c_int32)]
+
+
+EKS_ASSOC_MAX_OBS = 40      # 3k <= kEksMaxM
+
+
 class FSConfig(C.Structure):
     _fields_ = [("pf", PFConfig), ("r_dist", C.c_double), ("r_dir", C.c_double),
                 ("r_orient", C.c_double), ("use_orient", C.c_int32), ("pad0", C.c_int32)]
@@ -214,6 +227,16 @@ SIGNATURES = {
     "slam_ekfslam_step": (C.c_int, [_P, _D, C.c_int32, _I64, _D]),
     "slam_ekfslam_timing": (C.c_int, [_P, _D]),
     "slam_ekfslam_info": (C.c_int, [_P, C.POINTER(EKFSLAMInfo)]),
+    "slam_ekfslam_create_assoc": (C.c_int, [C.POINTER(EKFSLAMConfig), C.POINTER(EKFSLAMAssocConfig),
+                                            C.c_int64, C.c_int, C.POINTER(_P)]),
+    "slam_ekfslam_check_observations": (C.c_int, [C.c_int32, _D]),
+    "slam_ekfslam_observe": (C.c_int, [_P, C.c_int32, _D, _I32]),
+    "slam_ekfslam_step_assoc": (C.c_int, [_P, _D, C.c_int32, _D, _I32]),
+    "slam_ekfslam_get_count": (C.c_int, [_P, _I32]),
+    "slam_ekfslam_set_count": (C.c_int, [_P, C.c_int32]),
+    "slam_ekfslam_get_scores": (C.c_int, [_P, _D]),
+    "slam_ekfslam_assoc_info": (C.c_int, [_P, C.POINTER(EKFSLAMAssocInfo)]),
+    "slam_ekfslam_assoc_timing": (C.c_int, [_P, _D]),
     "slam_fs_check_observations": (C.c_int, [C.c_int32, C.c_int32, _I64, _D]),
     "slam_fs_create": (C.c_int, [C.POINTER(FSConfig), C.c_int64, C.c_int32, C.c_int, C.POINTER(_P)]),
     "slam_fs_destroy": (C.c_int, [_P]),

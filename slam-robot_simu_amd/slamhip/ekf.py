@@ -125,11 +125,22 @@ class DeviceEKF:
 
 
 class DeviceEKFSLAM:
-    """EKF-SLAM over ``n_landmarks`` landmarks (x, y, phi); covariance in HBM."""
+    """EKF-SLAM over ``n_landmarks`` landmarks (x, y, phi); covariance in HBM.
+
+    ``association="ml"``: ``n_landmarks`` is the capacity of a map that starts
+    empty.  ``observe(obs)`` / ``step(control, None, obs)`` take (range,
+    bearing, orientation) rows without ids: each is matched to the likeliest
+    landmark held (each landmark at most once per call) or, below ``p_new``,
+    starts a new one; the update then walks the ``3 + 3 count`` active rows
+    only.  ``record_assoc`` keeps the scores for ``last_scores()``."""
 
     def __init__(self, n_landmarks, *, dt=0.1, q_robot=None, noise=(0.05, np.deg2rad(2.0),
                                                                          np.deg2rad(2.0)), device=0,
-                 motion="linear", alphas=DEFAULT_ALPHAS):
+                 motion="linear", alphas=DEFAULT_ALPHAS, association=None, p_new=1e-4,
+                 record_assoc=False):
+        if association not in (None, "ml"):
+            raise ValueError(f"association must be None or 'ml', not {association!r}")
+        self.association = association
         cfg = EKFSLAMConfig()
         cfg.dt = float(dt)
         cfg.motion = _MOTIONS[motion]
@@ -142,8 +153,15 @@ class DeviceEKFSLAM:
         self.n = 3 + 3 * self.n_lm
         self._lib = _lib.load()
         h = C.c_void_p()
-        check(self._lib.slam_ekfslam_create(C.byref(cfg), self.n_lm, int(device), C.byref(h)),
-              "slam_ekfslam_create")
+        if association is None:
+            check(self._lib.slam_ekfslam_create(C.byref(cfg), self.n_lm, int(device), C.byref(h)),
+                  "slam_ekfslam_create")
+        else:
+            acfg = _lib.EKFSLAMAssocConfig(float(np.log(p_new)), int(bool(record_assoc)), 0)
+            check(self._lib.slam_ekfslam_create_assoc(C.byref(cfg), C.byref(acfg), self.n_lm,
+                                                      int(device), C.byref(h)),
+                  "slam_ekfslam_create_assoc")
+            self._assoc = np.empty(0, dtype=np.int32)
         self._h = h
 
     def close(self):
@@ -190,6 +208,15 @@ class DeviceEKFSLAM:
               "slam_ekfslam_update")
 
     def step(self, control, ids, obs):
+        """Predict and update.  ``ids=None`` (associating handle): the
+        observations carry no identity; returns the association."""
+        if ids is None:
+            obs = _f64(obs).reshape(-1, 3)
+            self._assoc = np.empty(obs.shape[0], dtype=np.int32)
+            check(self._lib.slam_ekfslam_step_assoc(
+                self._h, dptr(_f64(control, (2,))), int(obs.shape[0]), dptr(obs),
+                self._assoc.ctypes.data_as(C.POINTER(C.c_int32))), "slam_ekfslam_step_assoc")
+            return self._assoc.copy()
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         obs = _f64(obs, (ids.size, 3))
         check(self._lib.slam_ekfslam_step(self._h, dptr(_f64(control, (2,))), int(ids.size),
@@ -211,3 +238,60 @@ class DeviceEKFSLAM:
         return dict(n=s.n, ld=s.ld, n_pad=s.n_pad, n_tiles=s.n_tiles, frag_grid=s.frag_grid,
                     pipe_grid=s.pipe_grid, M=s.last_m, rank=_lib.EKS_RANK[s.last_rank],
                     apply=_lib.EKS_APPLY[s.last_apply])
+
+    # ------------------------------------------------ association="ml" only
+    def observe(self, obs):
+        """Associate, update and initialise from the current (predicted) state.
+        Returns assoc[k]: the slot matched, -1 for a new landmark, -2 dropped."""
+        obs = _f64(obs).reshape(-1, 3)
+        self._assoc = np.empty(obs.shape[0], dtype=np.int32)
+        check(self._lib.slam_ekfslam_observe(self._h, int(obs.shape[0]), dptr(obs),
+                                             self._assoc.ctypes.data_as(C.POINTER(C.c_int32))),
+              "slam_ekfslam_observe")
+        return self._assoc.copy()
+
+    @property
+    def count(self):
+        c = C.c_int32(0)
+        check(self._lib.slam_ekfslam_get_count(self._h, C.byref(c)), "slam_ekfslam_get_count")
+        return c.value
+
+    def set_count(self, count):
+        """With set_state, places a state: the caller keeps the tail at zero."""
+        check(self._lib.slam_ekfslam_set_count(self._h, int(count)), "slam_ekfslam_set_count")
+
+    def landmarks(self):
+        """(mean [count][3], cov [count][3][3]) of the landmarks held."""
+        cnt = self.count
+        mean = self.get_state(with_cov=False)[3:3 + 3 * cnt].reshape(cnt, 3)
+        cov = np.empty((cnt, 3, 3))
+        if cnt:
+            rows = self.get_rows(np.arange(3, 3 + 3 * cnt))
+            for j in range(cnt):
+                cov[j] = rows[3 * j:3 * j + 3, 3 + 3 * j:6 + 3 * j]
+        return mean, cov
+
+    def pose(self):
+        """(mu_r (3,), P_rr (3, 3))."""
+        return self.get_state(with_cov=False)[:3], self.get_rows([0, 1, 2])[:, :3]
+
+    def last_assoc(self):
+        return self._assoc.copy()
+
+    def last_scores(self):
+        """The last call's scores [k][count0] (``record_assoc=True``)."""
+        s = self.assoc_info()
+        out = np.empty((self._assoc.size, s["count0"]))
+        check(self._lib.slam_ekfslam_get_scores(self._h, dptr(out)), "slam_ekfslam_get_scores")
+        return out
+
+    def assoc_info(self):
+        s = _lib.EKFSLAMAssocInfo()
+        check(self._lib.slam_ekfslam_assoc_info(self._h, C.byref(s)), "slam_ekfslam_assoc_info")
+        return dict(n_act=s.n_act, tiles=s.tiles, count=s.count, count0=s.count0,
+                    matched=s.matched, new=s.created, dropped=s.dropped)
+
+    def assoc_timing(self):
+        out = np.zeros(4)
+        check(self._lib.slam_ekfslam_assoc_timing(self._h, dptr(out)), "slam_ekfslam_assoc_timing")
+        return dict(scan_ms=out[0], assign_ms=out[1], update_ms=out[2], init_ms=out[3])
