@@ -86,9 +86,12 @@ struct slam_pf {
     slam_pf_result* res_dev = nullptr;
     slam_pf_result* res_host = nullptr;   // pinned, coherent: the export kernel stores into it
     double* ctl_pin = nullptr;            // pinned, coherent staging of a batch's controls
-    slam_pf_result* res_host_dev = nullptr;   // the two pinned buffers' device addresses
+    slam_pf_result* res_host_dev = nullptr;   // the pinned buffers' device addresses
+    FinMoments* mom_dev = nullptr;        // [cap] raw totals of split step ends (pf_finalize.inl)
+    FinMoments* mom_host = nullptr;       // pinned, coherent: exported beside res_host
+    FinMoments* mom_host_dev = nullptr;
     double* ctl_pin_dev = nullptr;
-    int32_t* ctr = nullptr;               // [0] step in batch, [1] RNG step
+    int32_t* ctr = nullptr;               // [0] step in batch, [1] RNG step, [2..3] batch bounds, [4..5] kCtrMom
     int32_t z_steps = 0;
     LikConst lc;
     PredictConst pc;
@@ -223,6 +226,8 @@ int ensure_steps(slam_pf* h, int32_t steps) {
     m.release(h->truth);
     m.release(h->res_dev);
     m.release(h->res_host);
+    m.release(h->mom_dev);
+    m.release(h->mom_host);
     m.release(h->ctl_pin);
     h->cap = 0;
     int rc;
@@ -230,12 +235,13 @@ int ensure_steps(slam_pf* h, int32_t steps) {
     if ((rc = m.alloc(&h->ctl, 2 * (size_t)steps)) || (rc = m.alloc(&h->z_all, nlz * steps)) ||
         (rc = m.alloc(&h->zc, (size_t)kClosedWords * steps)) ||
         (rc = m.alloc(&h->ofs, (size_t)steps)) || (rc = m.alloc(&h->truth, 4 * (size_t)steps)) ||
-        (rc = m.alloc(&h->res_dev, (size_t)steps)))
+        (rc = m.alloc(&h->res_dev, (size_t)steps)) || (rc = m.alloc(&h->mom_dev, (size_t)steps)))
         return rc;
     // fine-grained host memory: the setup kernel reads the controls and the
     // export kernel stores the results over the host link, uncached
     const unsigned pin = hipHostMallocMapped | hipHostMallocCoherent;
     if ((rc = m.alloc_pinned(&h->res_host, &h->res_host_dev, (size_t)steps, pin)) ||
+        (rc = m.alloc_pinned(&h->mom_host, &h->mom_host_dev, (size_t)steps, pin)) ||
         (rc = m.alloc_pinned(&h->ctl_pin, &h->ctl_pin_dev, 2 * (size_t)steps, pin)))
         return rc;
     h->cap = steps;
@@ -347,8 +353,10 @@ int launch_fused(slam_pf* h, int motion, bool host_noise) {
     return SLAM_OK;
 }
 
-// numpy-order sum + normalise + reductions + result record res[ctr[0]]
-int launch_reduce(slam_pf* h, int32_t resampled_known) {
+// numpy-order sum + normalise + reductions + result record res[ctr[0]].
+// stepwise: the launch of a stepwise entry point (always the full step end);
+// a step of a device-resident batch (launch_step) decides on the device.
+int launch_reduce(slam_pf* h, int32_t resampled_known, bool stepwise = true) {
     const int64_t n = h->n;
     hipStream_t s = h->stream;
     const int c = h->cur;
@@ -361,10 +369,13 @@ int launch_reduce(slam_pf* h, int32_t resampled_known) {
     auto kern = !sliced ? finalize_fast_kernel<false>
                 : (h->fsl.nsl <= kFinFastSlices && n / kSumChunk <= 2048) ? finalize_fast_kernel<true>
                                                                           : finalize_general_kernel;
-    kern<<<1, kFinThreads, 0, s>>>(
+    // up to 2^20: one node of 1 + kFinMomGroups independent workgroups (the
+    // moment workgroups return at once on a full step end)
+    const FinSplit fs{h->mom_dev, h->mom_host_dev, c, stepwise ? 1 : 0};
+    kern<<<sliced ? 1 : 1 + kFinMomGroups, kFinThreads, 0, s>>>(
         n, h->dp, h->w_un, h->s_cur, h->tail_leaves, h->tail_ops, h->n_tail_leaves,
         h->n_tail_ops, h->x[c], h->y[c], h->th[c], h->refp, h->flags, h->cfg.ess_threshold,
-        step_io(h), resampled_known, h->pc.np_recip, h->boff, h->fsl);
+        step_io(h), resampled_known, h->pc.np_recip, h->boff, h->fsl, fs);
     toc(h, 1);
     SLAM_HIP_TRY(hipGetLastError());
     return SLAM_OK;
@@ -454,6 +465,8 @@ __global__ __launch_bounds__(512) void pf_run_setup_kernel(
         ctr[1] = stepno;
         ctr[2] = first;
         ctr[3] = first + nsteps - 1;
+        ctr[kCtrMom] = first;           // the step as the finalize's moment workgroups read it
+        ctr[kCtrMom + 1] = first;
         if (rflag >= 0) flags[kFlagResample] = rflag;
     }
     if (prep)
@@ -555,7 +568,7 @@ int launch_step(slam_pf* h, bool host_noise) {
 #endif
     toc(h, 2);
     if ((rc = launch_fused(h, h->cfg.motion, host_noise))) return rc;
-    return launch_reduce(h, -1);
+    return launch_reduce(h, -1, false);
 }
 
 // The records of steps [first, first + count) from the coherent host buffer:
@@ -732,7 +745,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     if (A(h->tk, 4 * kTicketWords)) return rc;
     if (A(h->lm, 2 * std::max<int32_t>(n_landmarks, 1))) return rc;
     if (A(h->noise, 3 * n)) return rc;
-    if (A(h->ctr, 4)) return rc;
+    if (A(h->ctr, kCtrWords)) return rc;
     std::vector<int32_t> leaves, ops;
     const int tail = (int)(n % kSumChunk);
     if (tail) pairwise_sum_split(0, tail, leaves, ops);
@@ -766,6 +779,7 @@ int create_impl(const slam_pf_config* cfg, int64_t n_local, int64_t n_global, in
     SLAM_HIP_TRY(hipMemset(h->tk, 0, 4 * kTicketWords * sizeof(unsigned)));
     SLAM_HIP_TRY(hipMemset(h->ctr, 0, 2 * sizeof(int32_t)));
     SLAM_HIP_TRY(hipMemsetD32((hipDeviceptr_t)(h->ctr + 2), -1, 2));   // no batch bounds yet
+    SLAM_HIP_TRY(hipMemset(h->ctr + kCtrMom, 0, 2 * sizeof(int32_t)));
     if (n_landmarks > 0)
         SLAM_HIP_TRY(hipMemcpy(h->lm, landmarks, 2 * n_landmarks * sizeof(double), hipMemcpyHostToDevice));
     *out = hp.release();
@@ -1166,6 +1180,13 @@ int slam_pf_run(slam_pf* h, int32_t first_step, int32_t n_steps, const double* c
         }
     }
     rc = sync_results(h, first_step, n_steps, results, true);
+    if (results && h->fsl.nsl <= 1) {
+        // the records of the batch's split step ends: cov from the step's raw
+        // totals, the expression the full step end uses (pf_kernels.hpp)
+        const FinMoments* mo = h->mom_host + first_step;
+        for (int32_t i = 0; i < n_steps; ++i)
+            if (mo[i].state == kMomPending) cov_from_totals(mo[i].tot, results[i].max_val, results[i].cov);
+    }
     if (rc == SLAM_OK && prep_next >= 0) {
         h->prep_step = prep_next;
         h->prep_ctl[0] = controls[2 * (n_steps - 1)];

@@ -22,12 +22,16 @@
 // takes a slow whole-array pass.
 
 #ifdef SLAM_FIN_PROBE
+// [0..5]: the phases of a full step end; [16..21]: of a split one (workgroup
+// 0); [24 + g]: the end of moment workgroup g of a split one
 __device__ long long g_fin_probe[32];
-#define FIN_STAMP(k) do { if (threadIdx.x == 0) g_fin_probe[k] = wall_clock64(); } while (0)
+#define FIN_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_fin_probe[k] = wall_clock64(); } while (0)
 #define FIN_STAMP_IF(c, k) do { if (c) g_fin_probe[k] = wall_clock64(); } while (0)
+#define FIN_STAMP_AT(base, k) FIN_STAMP((base) + (k))
 #else
 #define FIN_STAMP(k) do { } while (0)
 #define FIN_STAMP_IF(c, k) do { } while (0)
+#define FIN_STAMP_AT(base, k) do { } while (0)
 #endif
 
 #ifndef SLAM_FIN_THREADS
@@ -402,7 +406,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     const double* __restrict__ xs, const double* __restrict__ ys, const double* __restrict__ ts,
     double* __restrict__ refp, int32_t* __restrict__ flags, const double ess_th, StepIO io,
     const int32_t resampled_known, const double np_recip, double* __restrict__ boff,
-    const FinSlices sl) {
+    const FinSlices sl, const FinSplit fs) {
     __shared__ double sh[2048];                      // buffer sums / tail leaves / block totals
     __shared__ double s_q[11][kFinThreads];
     __shared__ BlockPartial shp[kFinWaves];
@@ -727,8 +731,104 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
 // sums and argmax candidate lists are fetched in the same first round trip,
 // so the chain runs over every buffer from LDS and the argmax checks the
 // listed candidates instead of walking the blocks beyond the registers.
+//
+// NP <= 2^20 (!SLICED), the split step end: a step inside a device-resident
+// batch, before the batch's last, runs as 1 + kFinMomGroups workgroups with
+// no hand-off between them.  Workgroup 0 is the step end: it loads the
+// leaves, pmax and ps(0..1) only (10 of the 28 loads per lane) and writes
+// everything the next kernel needs and the record without its cov.  The
+// covariance moments ps(2..10), which nothing on the device reads, go to the
+// moment workgroups (fin_moment_group): each reduces its share exactly as the
+// full path does and stores the raw totals relative to M into the step's
+// FinMoments entry; the record's reader forms cov from them
+// (cov_from_totals; slam_pf_run after its wait).  The batch's last step and
+// every stepwise launch take the full path in workgroup 0 (complete records,
+// the moment workgroups return at once), as does a degenerate step (!ok),
+// whose entry workgroup 0 marks complete.
 constexpr int kFinFastSlices = 16;          // SLICED: NP <= 2^24
 constexpr int kFinSlBuf = 4;                // SLICED: slice buffer values per lane (nfull <= 2048)
+constexpr int kFinMomGroups = 3;            // moment workgroups of a split step end
+constexpr int kFinMomPer = 9 / kFinMomGroups;   // of ps(2..10) each
+static_assert(kFinMomGroups * kFinMomPer == 9 && kFinMomPer <= kFinWaves, "ps(2..10), a wave per sum");
+
+// full step end: a stepwise launch, or a step that is not strictly inside a
+// batch before its last step (ctr[2..3]: the batch's bounds, -1 without one)
+__device__ __forceinline__ bool fin_full_path(const int32_t full, const int32_t st,
+                                              const int32_t b_first, const int32_t b_last) {
+    return full != 0 || !(b_first <= st && st < b_last);
+}
+
+// Moment workgroup g of a split step end: ps(2 + g kFinMomPer ...) over the
+// lane layout of fin_blk, scaled to the lane's max, rescaled to M, reduced in
+// the full path's order (per quantity: the same bits), stored raw.
+__device__ void fin_moment_group(const int g, const int64_t nb, const DeferParts& dp,
+                                 const StepIO& io, const FinSplit& fs, double (*s_q)[kFinThreads],
+                                 double* s_wmax) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t st = io.ctr[kCtrMom + fs.par], b_first = io.ctr[2], b_last = io.ctr[3];
+    double pm[kFinRegBlocks], q[kFinRegBlocks][kFinMomPer];
+    bool has[kFinRegBlocks];
+#pragma unroll
+    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
+        const int64_t b = fin_blk(tid, 2 * kp);
+        has[2 * kp] = b < nb;
+        has[2 * kp + 1] = b + 1 < nb;
+        const int64_t bb = has[2 * kp] ? b : 0;
+        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
+        pm[2 * kp] = t.x;
+        pm[2 * kp + 1] = t.y;
+#pragma unroll
+        for (int j = 0; j < kFinMomPer; ++j) {
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(2 + g * kFinMomPer + j) + bb);
+            q[2 * kp][j] = u.x;
+            q[2 * kp + 1][j] = u.y;
+        }
+    }
+    __asm__ volatile("" ::: "memory");                  // requested before the step is looked at
+    if (fin_full_path(fs.full, st, b_first, b_last) || st >= io.cap) return;
+    double mlane = -1.0;
+#pragma unroll
+    for (int k = 0; k < kFinRegBlocks; ++k)
+        if (has[k]) mlane = fmax(mlane, pm[k]);
+    const double wm = wave_max_f64(mlane);
+    if (lane == 0) s_wmax[wave] = wm;
+    double acc[kFinMomPer];
+#pragma unroll
+    for (int j = 0; j < kFinMomPer; ++j) acc[j] = 0.0;
+    if (mlane > 0.0) {
+        const double rm = 1.0 / mlane;
+#pragma unroll
+        for (int k = 0; k < kFinRegBlocks; ++k) {
+            if (has[k]) {
+                const double r = pm[k] * rm;
+#pragma unroll
+                for (int j = 0; j < kFinMomPer; ++j) acc[j] += r * q[k][j];
+            }
+        }
+    }
+    __syncthreads();                                     // s_wmax
+    double M = s_wmax[0];
+#pragma unroll
+    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
+    {
+        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
+#pragma unroll
+        for (int j = 0; j < kFinMomPer; ++j) s_q[j][tid] = acc[j] * rl;
+    }
+    __syncthreads();
+    if (wave < kFinMomPer) {
+        double r = s_q[wave][lane];
+#pragma unroll
+        for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[wave][lane + 64 * m];
+        r = wave_sum_rows(r);
+        if (lane == 0) fs.mom[st].tot[2 + g * kFinMomPer + wave] = r;
+    }
+#ifdef SLAM_FIN_PROBE
+    __syncthreads();
+    if (tid == 0) g_fin_probe[24 + g] = wall_clock64();
+#endif
+}
+
 template <bool SLICED>
 __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     const int64_t n, const DeferParts dp, const double* __restrict__ w_un,
@@ -737,7 +837,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     const double* __restrict__ xs, const double* __restrict__ ys, const double* __restrict__ ts,
     double* __restrict__ refp, int32_t* __restrict__ flags, const double ess_th, StepIO io,
     const int32_t resampled_known, const double np_recip, double* __restrict__ boff,
-    const FinSlices sl) {
+    const FinSlices sl, const FinSplit fs) {
     static_assert(kFinThreads == 512 && kFinRegBlocks == 4, "the register layout of fin_blk");
     static_assert(kFinSlBuf * kFinThreads + kFinBufPerRound >= 2048, "every buffer of sh");
     static_assert((kFinFastSlices - 1) * 11 <= kFinThreads, "one slice sum per lane");
@@ -764,21 +864,34 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     const int64_t nb = (n + kPartPer - 1) / kPartPer;
     const int64_t nfull = n / kSumChunk;
     const int64_t nch = (n + kSumChunk - 1) / kSumChunk;
-    FIN_STAMP(0);
-    // the step, the batch's bounds and the flag words the record reads: lane 0,
-    // first in its load queue (used at the end; the wait counts only them)
-    int32_t st_now = 0, b_first = 0, b_last = -1, rstep = 0;
-    FlagWords fw{};
-    double rp[3] = {0.0, 0.0, 0.0};
+    if constexpr (!SLICED) {
+        if (blockIdx.x > 0) {
+            fin_moment_group((int)blockIdx.x - 1, nb, dp, io, fs, s_q, s_wmax);
+            return;
+        }
+    }
+#ifdef SLAM_FIN_PROBE
+    const long long probe_t0 = wall_clock64();
+#endif
+    // the step, the batch's bounds, the flag words and the reference the
+    // record reads: every lane loads the same words into its own registers,
+    // first in its queue, and waits for them only where they are used (the
+    // path decision after the loads are out, the record at the end) --
+    // through an offset the compiler cannot see as uniform, or it reads them
+    // into scalar registers at once, a round trip ahead of the leaves on the
+    // wave that runs the chain
+    int uni_ofs = 0;
+    __asm__ volatile("" : "+v"(uni_ofs));
+    const int4 cw = *reinterpret_cast<const int4*>(io.ctr + uni_ofs);
+    const int32_t st_now = cw.x, rstep = cw.y, b_first = cw.z, b_last = cw.w;
+    static_assert(kFlagResample == 0 && kFlagStatus == 1 && kFlagNSpecial == 2 && kFlagMarkGen == 4 &&
+                      kFlagDDWaves == 7 && kFlagWords == 8, "the flag words as two 16-byte loads");
+    const int4 fa = *reinterpret_cast<const int4*>(flags + uni_ofs);
+    const int4 fb = *reinterpret_cast<const int4*>(flags + 4 + uni_ofs);
+    const FlagWords fw{fa.x, fa.y, fa.z, fb.w, fb.x};
+    const double2 rp01 = *reinterpret_cast<const double2*>(refp + uni_ofs);
+    const double rp[3] = {rp01.x, rp01.y, refp[2 + uni_ofs]};
     if (tid == 0) {
-        st_now = io.ctr[0];
-        rstep = io.ctr[1];
-        b_first = io.ctr[2];
-        b_last = io.ctr[3];
-        fw = load_flag_words(flags);
-        rp[0] = refp[0];
-        rp[1] = refp[1];
-        rp[2] = refp[2];
         s_ncand = 0;
         s_min = ~0ull;
         s_flag = 0;
@@ -820,17 +933,40 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         pm[2 * kp + 1] = t.y;
     }
     __asm__ volatile("" ::: "memory");                  // then the partial sums
+    auto load_ps = [&](const int j0, const int j1) {
 #pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-        const int64_t b = fin_blk(tid, 2 * kp);
-        const int64_t bb = b < nb ? b : 0;
+        for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
+            const int64_t b = fin_blk(tid, 2 * kp);
+            const int64_t bb = b < nb ? b : 0;
 #pragma unroll
-        for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
-            q[2 * kp][j] = u.x;
-            q[2 * kp + 1][j] = u.y;
+            for (int j = j0; j < j1; ++j) {
+                const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
+                q[2 * kp][j] = u.x;
+                q[2 * kp + 1][j] = u.y;
+            }
+        }
+    };
+    load_ps(0, 2);                                      // sum u (the prefix), sum u^2 (the ESS)
+    // the covariance moments: here on the full path only (a split step end
+    // leaves them to the moment workgroups); the path is known once the step
+    // counters are in, by when every load above is out
+    __asm__ volatile("" ::: "memory");
+    const bool full = SLICED || __builtin_amdgcn_readfirstlane((int)(
+        fin_full_path(fs.full, st_now, b_first, b_last) || st_now >= io.cap)) != 0;
+    const int nq = full ? 11 : 2;
+    if (full) {
+        load_ps(2, 11);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kFinRegBlocks; ++k) {
+#pragma unroll
+            for (int j = 2; j < 11; ++j) q[k][j] = 0.0;
         }
     }
+#ifdef SLAM_FIN_PROBE
+    const int pb = full ? 0 : 16;
+    if (tid == 0) g_fin_probe[pb] = probe_t0;
+#endif
     // SLICED: the slices' maxima, candidate lists and sums
     double slm = -1.0, slq = 0.0, ccp = -1.0, slu = 0.0;
     int64_t ccb = -1;
@@ -877,7 +1013,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         }
     }
     __syncthreads();                                     // sh
-    FIN_STAMP(1);
+    FIN_STAMP_AT(pb, 1);
     double s = 0.0;
     if (tid == 0 && nfull > 0) {
         // the buffers left to right while the other waves take their partials
@@ -927,8 +1063,10 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
                 const double r = pm[k] * rm;
                 acc[0] += r * q[k][0];
                 acc[1] += (r * r) * q[k][1];
+                if (full) {
 #pragma unroll
-                for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
+                    for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
+                }
             }
         }
     }
@@ -940,10 +1078,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
         acc[0] *= rl;
         acc[1] *= rl * rl;
+        s_q[0][tid] = acc[0];
+        s_q[1][tid] = acc[1];
+        if (full) {
 #pragma unroll
-        for (int j = 2; j < 11; ++j) acc[j] *= rl;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) s_q[j][tid] = acc[j];
+            for (int j = 2; j < 11; ++j) s_q[j][tid] = acc[j] * rl;
+        }
     }
     if (cblk >= 0 && cpm >= M * (1.0 - 0x1p-48)) {
         const int slot = atomicAdd(&s_ncand, 1);
@@ -972,14 +1112,15 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     if (tid == 0) s_s = s;
     __syncthreads();
     s = s_s;
-    FIN_STAMP(2);
+    FIN_STAMP_AT(pb, 2);
     const bool ok = (s > 0.0) && !isinf(s) && (M > 0.0);
     BlockPartial tot;
     bp_zero(tot);
     if (ok) {
         // ---- the 11 sums: wave w reduces quantities w and w + 8 (lane-strided
         // reads, then the wave's rows by DPP: a fixed order, no LDS permutes)
-        for (int j = wave; j < 11; j += kFinWaves) {
+        // (a split step end: sum u and sum u^2 only, one round)
+        for (int j = wave; j < nq; j += kFinWaves) {
             double r = s_q[j][lane];
 #pragma unroll
             for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[j][lane + 64 * m];
@@ -1067,10 +1208,15 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             const double f = M / s;                      // back from max-relative to w_un / s
             tot.maxv = mval;
             tot.maxi = s_mi;
-            tot.sw = s_tot[0] * f;
             tot.sw2 = s_tot[1] * (f * f);
-            for (int j = 0; j < 3; ++j) tot.m1[j] = s_tot[2 + j] * f;
-            for (int j = 0; j < 6; ++j) tot.m2[j] = s_tot[5 + j] * f;
+            if (full) {
+                moments_from_totals(s_tot, f, tot.sw, tot.m1, tot.m2);
+            } else {
+                // split: the raw totals this workgroup holds; the moment
+                // workgroups store theirs, the record's reader forms cov
+                fs.mom[st_now].tot[0] = s_tot[0];
+                fs.mom[st_now].tot[1] = s_tot[1];
+            }
         }
     } else {
         // ---- every weight through the reference's division (slow, degenerate case)
@@ -1098,25 +1244,42 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             s_xe[2] = ts[tot.maxi];
         }
     }
-    FIN_STAMP(3);
-    __shared__ int32_t s_exp[3];
+    FIN_STAMP_AT(pb, 3);
+    // the batch's last step exports the batch's records (a full step end)
+    const bool exp = io.res_host != nullptr && st_now == b_last && b_first <= b_last;
     if (tid == 0) {
-        const bool exp = io.res_host != nullptr && st_now == b_last && b_first <= b_last;
-        s_exp[0] = exp ? 1 : 0;
-        s_exp[1] = b_first;
-        s_exp[2] = st_now;
+        // the record holds its cov unless this is a split step end that went well
+        const bool with_cov = full || !ok;
         s_next = write_result_fw(tot, s_xe, refp, rp, s, flags, fw, ess_th, io.ess_band,
-                                 io.res + st_now, resampled_known, exp ? io.res_host + st_now : nullptr);
+                                 io.res + st_now, resampled_known, exp ? io.res_host + st_now : nullptr,
+                                 with_cov);
+        if constexpr (!SLICED) {
+            if (st_now < io.cap) {
+                fs.mom[st_now].state = with_cov ? kMomComplete : kMomPending;
+                if (exp) fs.mom_host[st_now].state = kMomComplete;
+            }
+            io.ctr[kCtrMom + (1 - fs.par)] = st_now + 1;   // the next launch's moment workgroups
+        }
         io.ctr[0] = st_now + 1;
         io.ctr[1] = rstep + 1;
         *s_cur = s;
     }
     __syncthreads();
-    FIN_STAMP(4);
-    if (s_exp[0] && tid >= 1 && tid < 64) {
+    FIN_STAMP_AT(pb, 4);
+    if (exp && tid >= 1 && tid < 64) {
         // the batch's earlier records (stored by earlier launches) to the host
         // buffer; this step's record went there from write_result_fw
-        for (int32_t k = s_exp[1] + tid - 1; k < s_exp[2]; k += 63) io.res_host[k] = io.res[k];
+        for (int32_t k = b_first + tid - 1; k < st_now; k += 63) io.res_host[k] = io.res[k];
+    }
+    if constexpr (!SLICED) {
+        if (exp && tid >= 64) {
+            // and their moment entries (complete by the kernel boundary), as words
+            constexpr int kW = (int)(sizeof(FinMoments) / 8);
+            const uint64_t* src = reinterpret_cast<const uint64_t*>(fs.mom + b_first);
+            uint64_t* dst = reinterpret_cast<uint64_t*>(fs.mom_host + b_first);
+            const int32_t words = (st_now - b_first) * kW;
+            for (int32_t k = tid - 64; k < words; k += kFinThreads - 64) dst[k] = src[k];
+        }
     }
     if (s_next) {
         double q0[kFinRegBlocks];
@@ -1196,5 +1359,5 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             fin_next_prefix(n, nb, ok, s, np_recip, pm, q0, has, w_un, dp, boff, sh, &s_q[0][0]);
         }
     }
-    FIN_STAMP(5);
+    FIN_STAMP_AT(pb, 5);
 }

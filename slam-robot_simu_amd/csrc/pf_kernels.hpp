@@ -139,6 +139,62 @@ struct BlockPartial {
     double m2[6];
 };
 
+// The record's weighted covariance from the combined moments (sw = sum w,
+// m1 = sum w d, m2 = sum w d d^T, upper triangle): one expression for the
+// step end and for the host, which completes the records of a batch's split
+// step ends (both built with -ffp-contract=off: the same bits).
+__host__ __device__ inline void cov_from_moments(const double sw, const double (&m1)[3],
+                                                 const double (&m2s)[6], double* cov) {
+    const double inv = 1.0 / sw;
+    const double mu[3] = {m1[0] * inv, m1[1] * inv, m1[2] * inv};
+    const double m2[9] = {m2s[0], m2s[1], m2s[2], m2s[1], m2s[3], m2s[4], m2s[2], m2s[4], m2s[5]};
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) cov[3 * a + b] = m2[3 * a + b] * inv - mu[a] * mu[b];
+}
+
+// The moments from the step end's totals relative to the global max M
+// (tot[0] sum u, tot[2..4] sum u d, tot[5..10] sum u d d^T, u = w_un / M):
+// f = M / s, the record's max_val, brings them back to w = w_un / s.
+__host__ __device__ inline void moments_from_totals(const double* tot, const double f, double& sw,
+                                                    double (&m1)[3], double (&m2)[6]) {
+    sw = tot[0] * f;
+    for (int j = 0; j < 3; ++j) m1[j] = tot[2 + j] * f;
+    for (int j = 0; j < 6; ++j) m2[j] = tot[5 + j] * f;
+}
+
+__host__ __device__ inline void cov_from_totals(const double* tot, const double f, double* cov) {
+    double sw, m1[3], m2[6];
+    moments_from_totals(tot, f, sw, m1, m2);
+    cov_from_moments(sw, m1, m2, cov);
+}
+
+// Per-step raw totals of a split step end (finalize_fast_kernel<false>,
+// pf_finalize.inl), a step-indexed sibling of StepIO.res: workgroup 0 stores
+// tot[0..1] and the state, the moment workgroups tot[2..10].  pending: the
+// record's cov is cov_from_totals(tot, record.max_val); complete: the record
+// holds its cov already (a full or degenerate step end), tot is not read.
+enum : int32_t { kMomComplete = 0, kMomPending = 1 };
+struct FinMoments {
+    double tot[11];
+    int32_t state, pad;
+};
+static_assert(sizeof(FinMoments) % 8 == 0, "moment entries move as 8-byte words");
+
+// What the finalize launch carries besides StepIO (which the fused kernel
+// shares and which therefore stays as it is)
+struct FinSplit {
+    FinMoments* mom;        // [cap] device entries
+    FinMoments* mom_host;   // [cap] coherent pinned copy (device address), beside StepIO.res_host
+    int32_t par;            // ping-pong parity of the step: the moment workgroups read the
+                            // step from ctr[4 + par], workgroup 0 leaves the next one in
+                            // ctr[4 + (1 - par)] (no word read and written in one launch)
+    int32_t full;           // a stepwise launch: always the full path
+};
+
+// ctr words beyond StepIO's four: the step as the moment workgroups read it
+constexpr int kCtrMom = 4;
+constexpr int kCtrWords = 6;
+
 struct SpecialIn {
     int64_t idx;            // global element index
     uint64_t P;             // inclusive prefix of the integer increments

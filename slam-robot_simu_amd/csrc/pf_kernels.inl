@@ -740,22 +740,25 @@ __device__ __forceinline__ FlagWords load_flag_words(const int32_t* flags) {
                      flags[kFlagDDWaves], flags[kFlagMarkGen]};
 }
 
+// with_cov false (a split step end, pf_finalize.inl): the record's cov is
+// formed by its reader from the step's FinMoments; zeros here
 __device__ int32_t write_result_fw(const BlockPartial& r, const double* xe, double* refp,
                                 const double (&rp)[3], const double s, int32_t* flags,
                                 const FlagWords fw, const double ess_th,
                                 const double ess_band, slam_pf_result* res,
-                                const int32_t resampled_known, slam_pf_result* res_host = nullptr) {
+                                const int32_t resampled_known, slam_pf_result* res_host = nullptr,
+                                const bool with_cov = true) {
     slam_pf_result o;
     o.max_idx = r.maxi;
     o.max_val = r.maxv;
     o.x_est[0] = xe[0];
     o.x_est[1] = xe[1];
     o.x_est[2] = xe[2];
-    const double inv = 1.0 / r.sw;
-    const double mu[3] = {r.m1[0] * inv, r.m1[1] * inv, r.m1[2] * inv};
-    const double m2[9] = {r.m2[0], r.m2[1], r.m2[2], r.m2[1], r.m2[3], r.m2[4], r.m2[2], r.m2[4], r.m2[5]};
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) o.cov[3 * a + b] = m2[3 * a + b] * inv - mu[a] * mu[b];
+    if (with_cov) {
+        cov_from_moments(r.sw, r.m1, r.m2, o.cov);
+    } else {
+        for (int a = 0; a < 9; ++a) o.cov[a] = 0.0;
+    }
     o.ess = 1.0 / r.sw2;
     o.weight_sum = s;
     o.resampled = resampled_known >= 0 ? resampled_known : (fw.resample != 0);
