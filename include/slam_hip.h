@@ -440,8 +440,10 @@ int slam_ekfslam_info(slam_ekfslam* h, slam_ekfslam_info_t* out);
  *
  * An associating handle has a capacity cap (n = 3 + 3 cap) and holds
  * count <= cap landmarks in slots 0..count-1, in creation order; nothing is
- * removed.  Rows and columns of P and entries of mu at or beyond
- * n_act = 3 + 3 count are exactly zero and stay so.
+ * removed unless the handle prunes (slam_ekfslam_set_pruning, after the
+ * FastSLAM pruning block below; off by default) or the caller removes slots by
+ * hand (slam_ekfslam_remove).  Rows and columns of P and entries of mu at or
+ * beyond n_act = 3 + 3 count are exactly zero and stay so.
  *
  * slam_ekfslam_observe(h, k, obs, assoc_out) takes 0 <= k <= 40 observations
  * (range, bearing, orientation) without identity.  count0 is the count at
@@ -855,6 +857,72 @@ int slam_fs_set_evidence(slam_fs* h, const int32_t* ev);
 int slam_fs_get_evidence(slam_fs* h, int32_t* ev);
 /* removed[NP]: the last pass's removals per particle (0 before any pass) */
 int slam_fs_get_removed(slam_fs* h, int32_t* removed);
+
+/* --------------------------------------------------------------------
+ * EKF-SLAM without ids: landmark evidence and removal from the map (DESIGN
+ * 11h).  An optional mode of an associating slam_ekfslam handle, off by
+ * default: a handle that never turns it on launches what it launched before,
+ * with the same arguments.  The configuration is slam_fs_prune_config, checked
+ * by slam_fs_check_prune_config: both estimators take the same one.  Each slot
+ * j < count carries an int32 evidence value ev[j].
+ *
+ * The pass runs at the end of every slam_ekfslam_observe and
+ * slam_ekfslam_step_assoc, after steps 3 and 4 of the contract above, k = 0
+ * included: an empty scan is evidence too.  slam_ekfslam_update with ids leaves
+ * the evidence alone.  Let count0 be the count at entry, count the count after
+ * the initialisation and (x, y, th) the posterior robot pose mu[0..2].  For
+ * every slot j < count, in slot order:
+ *   1. j >= count0 (created by this call): ev = init;
+ *   2. an observation of this call matched the slot: ev = min(ev + hit, ev_max);
+ *   3. otherwise, with (mx, my) = mu[3 + 3 j], mu[4 + 3 j]: dx = mx - x,
+ *      dy = my - y, and with c, s = cos, sin(pi/2 - th): rx = c dx - s dy,
+ *      ry = s dx + c dy.  The landmark is in view when
+ *      dx dx + dy dy <= view_range view_range and, with use_angle, also
+ *      ry >= |rx| view_tan; a comparison with a NaN counts as not in view.  In
+ *      view: ev -= miss (the value saturates at INT32_MIN); out of view:
+ *      unchanged;
+ *   4. slots with ev < remove_below are removed.
+ * Removal: with keep the surviving old slots in order and
+ * idx = [0, 1, 2] + [3 + 3 j + a for j in keep, a in 0..2]: mu' = mu[idx],
+ * P' = P[idx][:, idx], ev' = ev[keep], all bit for bit, in place; everything at
+ * or beyond the new n_act is exactly zero again in mu and in the rows of the
+ * lower triangle that the handle stores (slam_ekfslam_get_state mirrors it),
+ * which restores the invariant above.
+ *
+ * assoc_out keeps the slot numbers in force during the update, before the
+ * compaction; slam_ekfslam_get_count, slam_ekfslam_assoc_info, the state
+ * accessors and slam_ekfslam_get_evidence report the state after it.  An
+ * observation dropped for lack of room stays dropped in that call: the slots
+ * the pass frees are there for the next one.
+ *
+ * slam_ekfslam_set_pruning: NULL turns the mode off; turning it on (from off)
+ * gives every live slot init; on a handle that already prunes the call only
+ * replaces the configuration.  SLAM_ERR_ARG before any HIP call for a NULL or
+ * known-id handle or a bad configuration.  slam_ekfslam_set_count on a pruning
+ * handle resets the live slots to init; slam_ekfslam_set_evidence then
+ * overrides.  set / get_evidence take int32[cap]: the slots at or beyond count
+ * are ignored by set and read 0 from get; SLAM_ERR_ARG while pruning is off.
+ *
+ * slam_ekfslam_remove(h, n, slots) removes the named slots now, whether the
+ * handle prunes or not (their evidence goes with them when it does): a map
+ * managed by hand.  slots must be strictly increasing and < count, else
+ * SLAM_ERR_ARG before any HIP call; n = 0 is a no-op.
+ * -------------------------------------------------------------------- */
+int slam_ekfslam_set_pruning(slam_ekfslam* h, const slam_fs_prune_config* cfg);
+int slam_ekfslam_set_evidence(slam_ekfslam* h, const int32_t* ev);
+int slam_ekfslam_get_evidence(slam_ekfslam* h, int32_t* ev);
+int slam_ekfslam_remove(slam_ekfslam* h, int32_t n, const int32_t* slots);
+
+typedef struct {
+    int32_t count_before;  /* of the last pass or slam_ekfslam_remove (0 before any) */
+    int32_t removed;
+    int32_t moved;         /* surviving slots that changed place */
+    int32_t first;         /* first removed slot, -1 if none */
+    double  evidence_ms;   /* device time of the evidence (or mask) kernel */
+    double  compact_ms;    /* ... of the compaction's launches (0: none ran) */
+} slam_ekfslam_prune_info_t;
+
+int slam_ekfslam_prune_info(slam_ekfslam* h, slam_ekfslam_prune_info_t* out);
 
 /* ====================================================================
  * Graph-based SLAM -- replaces TrajectoryEstimator's linearise-and-solve

@@ -13,6 +13,7 @@
 #include "device_mem.hpp"
 #include "ekf_kernels.inl"
 #include "ekf_assoc.inl"
+#include "eks_prune.hpp"
 
 using namespace slam;
 
@@ -71,6 +72,17 @@ struct slam_ekfslam {
     int32_t last_k = 0, last_count0 = 0;
     int32_t last_matched = 0, last_new = 0, last_dropped = 0;
     int64_t last_tiles = 0;        // tiles the last update walked
+    // landmark evidence and removal (slam_ekfslam_set_pruning / _remove; DESIGN
+    // 11h); buffers and events from the first use
+    bool prune = false;
+    slam_fs_prune_config prcfg{};
+    int32_t* evd = nullptr;        // n_lm: evidence of the slots below count
+    int32_t* psrc = nullptr;       // n_lm: the old slot of new slot w
+    int32_t* pmask = nullptr;      // n_lm: slam_ekfslam_remove's flags
+    int32_t* pres = nullptr;       // kEksPrWords
+    hipEvent_t pev[3] = {};
+    int32_t pr_before = 0, pr_removed = 0, pr_moved = 0, pr_first = -1;
+    double pr_ms[2] = {0, 0};      // evidence kernel, compaction
 
     // rows of the state in use: all of it, or an associating handle's prefix
     int64_t n_act() const { return assoc ? 3 + 3 * (int64_t)count : n; }
@@ -535,6 +547,71 @@ int eks_check_observations(const char* who, int32_t k, const double* obs) {
     return SLAM_OK;
 }
 
+// The buffers and events of the evidence pass and of slam_ekfslam_remove.
+int eks_prune_reserve(slam_ekfslam* h) {
+    if (h->psrc) return SLAM_OK;
+    DeviceMem& m = h->mem;
+    int rc;
+    if ((rc = m.alloc(&h->evd, (size_t)h->n_lm)) || (rc = m.alloc(&h->pmask, (size_t)h->n_lm)) ||
+        (rc = m.alloc(&h->pres, (size_t)kEksPrWords)) || (rc = m.event(&h->pev[0])) ||
+        (rc = m.event(&h->pev[1])) || (rc = m.event(&h->pev[2])) ||
+        (rc = m.alloc(&h->psrc, (size_t)h->n_lm)))
+        return rc;
+    return SLAM_OK;
+}
+
+// every slot at init: the slots at or beyond count are never read (a slot that
+// a call creates takes init)
+int eks_evidence_init(slam_ekfslam* h) {
+    SLAM_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->evd, h->prcfg.init, (size_t)h->n_lm, h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+// After the evidence or mask kernel (between pev[0] and pev[1]): the result
+// words to the host, the compaction where something was removed, the new count.
+int eks_prune_finish(slam_ekfslam* h, int32_t count) {
+    int32_t res[kEksPrWords];
+    SLAM_HIP_TRY(hipGetLastError());
+    SLAM_HIP_TRY(hipMemcpyAsync(res, h->pres, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    const int32_t cn = res[kEksPrCount], first = res[kEksPrFirst];
+    if (cn < 0 || cn > count || res[kEksPrRemoved] != count - cn ||
+        (cn < count) != (first >= 0 && first <= cn))
+        return fail(SLAM_ERR_STATE, "slam_ekfslam: inconsistent removal");
+    h->pr_before = count;
+    h->pr_removed = count - cn;
+    h->pr_moved = res[kEksPrMoved];
+    h->pr_first = first;
+    h->pr_ms[1] = 0.0;
+    float ms;
+    if (cn < count) {
+        eks_compact_launch(h->stream, h->P, h->ld, h->mu, h->psrc, first, cn, count);
+        SLAM_HIP_TRY(hipEventRecord(h->pev[2], h->stream));
+        SLAM_HIP_TRY(hipGetLastError());
+        SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+        SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->pev[1], h->pev[2]));
+        h->pr_ms[1] = ms;
+        h->count = cn;
+    }
+    SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->pev[0], h->pev[1]));
+    h->pr_ms[0] = ms;
+    return SLAM_OK;
+}
+
+// The evidence pass at the end of an observe (include/slam_hip.h); matched:
+// the assign kernel ran in this call and left its marks in taken.
+int eks_prune_pass(slam_ekfslam* h, int32_t count0, bool matched) {
+    const slam_fs_prune_config& pc = h->prcfg;
+    const EksPrune P{pc.view_range * pc.view_range, pc.view_tan, pc.init, pc.hit, pc.miss,
+                     pc.ev_max, pc.remove_below};
+    SLAM_HIP_TRY(hipEventRecord(h->pev[0], h->stream));
+    eks_evidence_launch(h->stream, pc.use_angle != 0, h->mu, count0, h->count,
+                        matched ? h->taken : nullptr, P, h->evd, h->psrc, h->pres);
+    SLAM_HIP_TRY(hipEventRecord(h->pev[1], h->stream));
+    return eks_prune_finish(h, h->count);
+}
+
 // Score, choose, update over the active prefix, initialise (include/slam_hip.h).
 int eks_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_out) {
     const EksConst c = eks_const(h->cfg);
@@ -545,7 +622,7 @@ int eks_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_ou
     h->last_matched = h->last_new = h->last_dropped = 0;
     h->last_tiles = 0;
     for (double& v : h->assoc_ms) v = 0.0;
-    if (k == 0) return SLAM_OK;
+    if (k == 0) return h->prune ? eks_prune_pass(h, count0, false) : SLAM_OK;   // an empty scan is evidence too
     SLAM_HIP_TRY(hipEventRecord(h->aev[0], h->stream));
     if (count0 > 0) {
         EksScan sc{};
@@ -616,7 +693,7 @@ int eks_observe(slam_ekfslam* h, int32_t k, const double* obs, int32_t* assoc_ou
         SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->aev[3], h->aev[4]));
         h->assoc_ms[3] = ms;
     }
-    return SLAM_OK;
+    return h->prune ? eks_prune_pass(h, count0, true) : SLAM_OK;
 }
 
 }  // namespace
@@ -663,6 +740,83 @@ int slam_ekfslam_set_count(slam_ekfslam* h, int32_t count) {
     SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_set_count: not an associating handle");
     SLAM_ARG_CHECK(count >= 0 && count <= h->n_lm, "slam_ekfslam_set_count: need 0 <= count <= capacity");
     h->count = count;
+    if (h->prune) {
+        SLAM_HIP_TRY(hipSetDevice(h->device));
+        return eks_evidence_init(h);
+    }
+    return SLAM_OK;
+}
+
+int slam_ekfslam_set_pruning(slam_ekfslam* h, const slam_fs_prune_config* c) {
+    SLAM_ARG_CHECK(h, "slam_ekfslam_set_pruning: NULL handle");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_set_pruning: not an associating handle");
+    if (!c) {
+        h->prune = false;
+        return SLAM_OK;
+    }
+    int rc = slam_fs_check_prune_config(c);
+    if (rc) return rc;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    if ((rc = eks_prune_reserve(h))) return rc;
+    const bool was = h->prune;
+    h->prcfg = *c;
+    h->prcfg.use_angle = c->use_angle ? 1 : 0;
+    h->prune = true;
+    return was ? SLAM_OK : eks_evidence_init(h);     // turned on: every live slot starts at init
+}
+
+int slam_ekfslam_set_evidence(slam_ekfslam* h, const int32_t* ev) {
+    SLAM_ARG_CHECK(h && ev, "slam_ekfslam_set_evidence: NULL argument");
+    SLAM_ARG_CHECK(h->prune, "slam_ekfslam_set_evidence: pruning is off");
+    if (h->count == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    SLAM_HIP_TRY(hipMemcpyAsync(h->evd, ev, sizeof(int32_t) * (size_t)h->count, hipMemcpyHostToDevice,
+                                h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+int slam_ekfslam_get_evidence(slam_ekfslam* h, int32_t* ev) {
+    SLAM_ARG_CHECK(h && ev, "slam_ekfslam_get_evidence: NULL argument");
+    SLAM_ARG_CHECK(h->prune, "slam_ekfslam_get_evidence: pruning is off");
+    std::fill(ev + h->count, ev + h->n_lm, 0);
+    if (h->count == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    SLAM_HIP_TRY(hipMemcpyAsync(ev, h->evd, sizeof(int32_t) * (size_t)h->count, hipMemcpyDeviceToHost,
+                                h->stream));
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return SLAM_OK;
+}
+
+int slam_ekfslam_remove(slam_ekfslam* h, int32_t n, const int32_t* slots) {
+    SLAM_ARG_CHECK(h, "slam_ekfslam_remove: NULL handle");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_remove: not an associating handle");
+    SLAM_ARG_CHECK(n >= 0 && (n == 0 || slots), "slam_ekfslam_remove: bad arguments");
+    for (int32_t q = 0; q < n; ++q)
+        SLAM_ARG_CHECK(slots[q] >= 0 && slots[q] < h->count && (q == 0 || slots[q] > slots[q - 1]),
+                       "slam_ekfslam_remove: slots must be strictly increasing and below count");
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    int rc = eks_prune_reserve(h);
+    if (rc) return rc;
+    std::vector<int32_t> mask((size_t)h->count, 0);
+    for (int32_t q = 0; q < n; ++q) mask[(size_t)slots[q]] = 1;
+    SLAM_HIP_TRY(hipMemcpyAsync(h->pmask, mask.data(), sizeof(int32_t) * mask.size(),
+                                hipMemcpyHostToDevice, h->stream));
+    SLAM_HIP_TRY(hipEventRecord(h->pev[0], h->stream));
+    eks_mask_launch(h->stream, h->pmask, h->count, h->prune ? h->evd : nullptr, h->psrc, h->pres);
+    SLAM_HIP_TRY(hipEventRecord(h->pev[1], h->stream));
+    return eks_prune_finish(h, h->count);
+}
+
+static_assert(sizeof(slam_ekfslam_prune_info_t) == 32,
+              "slamhip/_lib.py EKFSLAMPruneInfo mirrors this layout");
+
+int slam_ekfslam_prune_info(slam_ekfslam* h, slam_ekfslam_prune_info_t* out) {
+    SLAM_ARG_CHECK(h && out, "slam_ekfslam_prune_info: NULL argument");
+    SLAM_ARG_CHECK(h->assoc, "slam_ekfslam_prune_info: not an associating handle");
+    *out = slam_ekfslam_prune_info_t{h->pr_before, h->pr_removed, h->pr_moved, h->pr_first,
+                                     h->pr_ms[0], h->pr_ms[1]};
     return SLAM_OK;
 }
 

@@ -50,9 +50,11 @@ P0 = (1e-4, 1e-4, 1e-6)
 
 class EKFSLAM:
     """Keyword arguments are DeviceEKFSLAM's (dt, q_robot, noise=(r_dist, r_dir,
-    r_orient), motion, alphas, device, p_new, record_assoc); the measurement
-    noise defaults to ScanSensor's (10 %, 3 deg, 3 deg).  ``x0`` / ``p0``: the
-    start pose and the diagonal of its covariance."""
+    r_orient), motion, alphas, device, p_new, record_assoc, prune); the
+    measurement noise defaults to ScanSensor's (10 %, 3 deg, 3 deg).  ``x0`` /
+    ``p0``: the start pose and the diagonal of its covariance.
+    ``prune=dict(view_range=...)`` (FastSLAM's keywords) removes landmarks that
+    stay unmatched in view: ``count`` and ``map()`` then shrink as well."""
 
     def __init__(self, capacity, *, association="ml", x0=X0, p0=P0, **kw):
         kw.setdefault("noise", (0.1, np.deg2rad(3.0), np.deg2rad(3.0)))

@@ -101,6 +101,11 @@ class FSPruneConfig(C.Structure):
                 ("ev_max", C.c_int32), ("remove_below", C.c_int32)]
 
 
+class EKFSLAMPruneInfo(C.Structure):
+    _fields_ = [("count_before", C.c_int32), ("removed", C.c_int32), ("moved", C.c_int32),
+                ("first", C.c_int32), ("evidence_ms", C.c_double), ("compact_ms", C.c_double)]
+
+
 class GraphEdge(C.Structure):
     _fields_ = [("time_bfr", C.c_int64), ("pose_bfr", C.c_int64), ("time_aft", C.c_int64),
                 ("pose_aft", C.c_int64), ("obs_bfr", C.c_double * 3), ("obs_aft", C.c_double * 3)]
@@ -270,6 +275,11 @@ SIGNATURES = {
     "slam_fs_set_evidence": (C.c_int, [_P, _I32]),
     "slam_fs_get_evidence": (C.c_int, [_P, _I32]),
     "slam_fs_get_removed": (C.c_int, [_P, _I32]),
+    "slam_ekfslam_set_pruning": (C.c_int, [_P, C.POINTER(FSPruneConfig)]),
+    "slam_ekfslam_set_evidence": (C.c_int, [_P, _I32]),
+    "slam_ekfslam_get_evidence": (C.c_int, [_P, _I32]),
+    "slam_ekfslam_remove": (C.c_int, [_P, C.c_int32, _I32]),
+    "slam_ekfslam_prune_info": (C.c_int, [_P, C.POINTER(EKFSLAMPruneInfo)]),
     "slam_graph_create": (C.c_int, [C.POINTER(GraphConfig), C.c_int, C.POINTER(_P)]),
     "slam_graph_destroy": (C.c_int, [_P]),
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import EKFConfig, EKFSLAMConfig, check, dptr
+from .fastslam import prune_config
 
 
 def _f64(a, shape=None):
@@ -132,14 +133,23 @@ class DeviceEKFSLAM:
     bearing, orientation) rows without ids: each is matched to the likeliest
     landmark held (each landmark at most once per call) or, below ``p_new``,
     starts a new one; the update then walks the ``3 + 3 count`` active rows
-    only.  ``record_assoc`` keeps the scores for ``last_scores()``."""
+    only.  ``record_assoc`` keeps the scores for ``last_scores()``.
+
+    ``prune``: None, or ``set_pruning``'s keywords as a dict (DeviceFastSLAM's:
+    both estimators take the same ones) -- every landmark then carries an
+    evidence value, gains ``hit`` when matched, loses ``miss`` when it lies in
+    view of the posterior pose unmatched, and is removed from ``mu`` and ``P``
+    below ``remove_below``; the survivors move down in place.  ``remove(slots)``
+    takes landmarks away by hand."""
 
     def __init__(self, n_landmarks, *, dt=0.1, q_robot=None, noise=(0.05, np.deg2rad(2.0),
                                                                          np.deg2rad(2.0)), device=0,
                  motion="linear", alphas=DEFAULT_ALPHAS, association=None, p_new=1e-4,
-                 record_assoc=False):
+                 record_assoc=False, prune=None):
         if association not in (None, "ml"):
             raise ValueError(f"association must be None or 'ml', not {association!r}")
+        if prune is not None and association is None:
+            raise ValueError("prune needs association='ml'")
         self.association = association
         cfg = EKFSLAMConfig()
         cfg.dt = float(dt)
@@ -163,6 +173,13 @@ class DeviceEKFSLAM:
                   "slam_ekfslam_create_assoc")
             self._assoc = np.empty(0, dtype=np.int32)
         self._h = h
+        self.prune = None
+        if prune is not None:
+            try:
+                self.set_pruning(**prune)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -295,3 +312,50 @@ class DeviceEKFSLAM:
         out = np.zeros(4)
         check(self._lib.slam_ekfslam_assoc_timing(self._h, dptr(out)), "slam_ekfslam_assoc_timing")
         return dict(scan_ms=out[0], assign_ms=out[1], update_ms=out[2], init_ms=out[3])
+
+    def set_pruning(self, view_range=None, **kw):
+        """Landmark evidence and removal (slam_ekfslam_set_pruning):
+        ``set_pruning(view_range, view_angle=None, init=1, hit=1, miss=1,
+        ev_max=2**31 - 1, remove_below=0)`` turns it on (every live slot starts
+        at ``init``) or replaces the configuration; ``set_pruning(None)`` turns
+        it off.  The pass runs at the end of every ``observe`` / ``step`` without
+        ids, an empty scan included."""
+        if self.association is None:
+            raise ValueError("set_pruning needs association='ml'")
+        if view_range is None:
+            if kw:
+                raise ValueError("set_pruning(None) takes no other argument")
+            check(self._lib.slam_ekfslam_set_pruning(self._h, None), "slam_ekfslam_set_pruning")
+            self.prune = None
+            return
+        cfg = prune_config(view_range, **kw)
+        check(self._lib.slam_ekfslam_set_pruning(self._h, C.byref(cfg)), "slam_ekfslam_set_pruning")
+        self.prune = cfg
+
+    def evidence(self):
+        """The evidence of every slot, [n_landmarks] int32; 0 at and above the count."""
+        e = np.empty(self.n_lm, dtype=np.int32)
+        check(self._lib.slam_ekfslam_get_evidence(self._h, e.ctypes.data_as(_lib._I32)),
+              "slam_ekfslam_get_evidence")
+        return e
+
+    def set_evidence(self, ev):
+        e = np.ascontiguousarray(ev, dtype=np.int32).reshape(self.n_lm)
+        check(self._lib.slam_ekfslam_set_evidence(self._h, e.ctypes.data_as(_lib._I32)),
+              "slam_ekfslam_set_evidence")
+
+    def remove(self, slots):
+        """Remove the landmarks in ``slots`` (strictly increasing, below the
+        count) from mu, P and the evidence now; the survivors keep their order."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        check(self._lib.slam_ekfslam_remove(self._h, int(s.size), s.ctypes.data_as(_lib._I32)),
+              "slam_ekfslam_remove")
+
+    def prune_info(self):
+        """The last pass or ``remove``: the count before it, landmarks removed,
+        surviving slots moved, the first removed slot (-1: none) and the device
+        ms of the evidence kernel and of the compaction."""
+        s = _lib.EKFSLAMPruneInfo()
+        check(self._lib.slam_ekfslam_prune_info(self._h, C.byref(s)), "slam_ekfslam_prune_info")
+        return dict(count_before=s.count_before, removed=s.removed, moved=s.moved, first=s.first,
+                    evidence_ms=s.evidence_ms, compact_ms=s.compact_ms)
