@@ -9,9 +9,6 @@
 #include "fastslam.inl"
 #include "fs_prune.hpp"
 
-static_assert(slam::kFsPruneThreads == slam::kFsThreads && slam::kFsPruneComp == slam::kFsComp,
-              "fs_prune.hip walks fastslam.inl's layout");
-
 struct slam_fs {
     slam_fs_config cfg;
     slam_pf* pf = nullptr;                 // the inner filter: destroyed with this handle

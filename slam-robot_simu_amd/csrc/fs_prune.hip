@@ -2,30 +2,19 @@
 // unsupported landmarks on an associating FastSLAM handle (include/slam_hip.h,
 // slam_fs_set_pruning), with their launchers (fs_prune.hpp).
 //
-// A translation unit of its own, not a part of fastslam.inl: pf_api's code
-// object -- the particle filter's and every older FastSLAM kernel -- then stays
-// byte for byte what it was, placement included (time bars).
+// A translation unit of its own, not a part of fastslam.inl: a change here
+// leaves pf_api's code object -- the particle filter's and the other FastSLAM
+// kernels -- byte for byte what it was, placement included (time
+// bars).  What the two share is fs_common.hpp.
 //
-// Map layout as fastslam.inl's: map[(5 j + c) * npad + p]; the evidence and the
-// match stamps are rows [cap][npad] of int32.
+// Map layout: fs_common.hpp; the evidence and the match stamps are rows
+// [cap][npad] of int32.
 #include <cstdint>
 
+#include "fs_common.hpp"
 #include "fs_prune.hpp"
 
 namespace slam {
-
-namespace {
-
-__device__ __forceinline__ int32_t fs_wave_max_i32(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int32_t u = __shfl_xor(v, o, 64);
-        v = u > v ? u : v;
-    }
-    return v;
-}
-
-}  // namespace
 
 // One lane per particle; the wave walks the slots below its largest count.
 // Every lane loads the row's mx, my, stamp and evidence (coalesced rows, lanes
@@ -36,14 +25,13 @@ __device__ __forceinline__ int32_t fs_wave_max_i32(int32_t v) {
 // loaded on those lanes alone.  Writes the counts, removed and the block maxima
 // of the new counts.  Padding lanes hold nothing and store nothing.
 template <bool ANGLE>
-__global__ __launch_bounds__(kFsPruneThreads) void fs_prune_kernel(
+__global__ __launch_bounds__(kFsThreads) void fs_prune_kernel(
     const int64_t n, const int64_t npad, const double* __restrict__ xs,
     const double* __restrict__ ys, const double* __restrict__ ts, double* __restrict__ map,
     int32_t* __restrict__ cnt_io, const int32_t* __restrict__ cnt_before,
     const int32_t* __restrict__ stamp, const int32_t call, const int32_t cap, const FsPrune P,
     int32_t* __restrict__ ev, int32_t* __restrict__ removed, int32_t* __restrict__ bcnt) {
-    __shared__ int32_t s_cmax[kFsPruneThreads / 64];
-    const int64_t p = (int64_t)blockIdx.x * kFsPruneThreads + threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
     const bool valid = p < n;
     const int64_t pc = valid ? p : n - 1;
     const double x = xs[pc], y = ys[pc];
@@ -52,12 +40,12 @@ __global__ __launch_bounds__(kFsPruneThreads) void fs_prune_kernel(
     int32_t cnt = valid ? cnt_io[p] : 0;
     cnt = cnt < cap ? cnt : cap;
     const int32_t cnt0 = cnt_before[pc];
-    const int32_t jmax = __builtin_amdgcn_readfirstlane(fs_wave_max_i32(cnt));
+    const int32_t jmax = __builtin_amdgcn_readfirstlane(fs_wave_max(cnt));
     int32_t w = 0;
     for (int32_t j = 0; j < jmax; ++j) {
         const size_t erow = (size_t)j * (size_t)npad + (size_t)pc;
-        const size_t row = (size_t)kFsPruneComp * (size_t)j * (size_t)npad + (size_t)pc;
-        const double mx = map[row], my = map[row + (size_t)npad];
+        const double* m = fs_row(map, j, npad, pc);
+        const double mx = m[0], my = m[(size_t)npad];
         const int32_t st = stamp[erow];
         int64_t e = ev[erow];
         if (j >= cnt0) {
@@ -81,14 +69,7 @@ __global__ __launch_bounds__(kFsPruneThreads) void fs_prune_kernel(
             const size_t wrow = (size_t)w * (size_t)npad + (size_t)pc;
             ev[wrow] = (int32_t)e;
             if (w < j) {
-                const double pxx = map[row + 2 * (size_t)npad], pxy = map[row + 3 * (size_t)npad],
-                             pyy = map[row + 4 * (size_t)npad];
-                double* m = map + (size_t)kFsPruneComp * (size_t)w * (size_t)npad + (size_t)pc;
-                m[0] = mx;
-                m[(size_t)npad] = my;
-                m[2 * (size_t)npad] = pxx;
-                m[3 * (size_t)npad] = pxy;
-                m[4 * (size_t)npad] = pyy;
+                fs_row_copy(m, fs_row(map, w, npad, pc), npad);
             }
             ++w;
         }
@@ -97,43 +78,28 @@ __global__ __launch_bounds__(kFsPruneThreads) void fs_prune_kernel(
         cnt_io[p] = w;
         removed[p] = cnt - w;
     }
-    const int32_t cm = fs_wave_max_i32(w);
-    if ((threadIdx.x & 63) == 0) s_cmax[threadIdx.x >> 6] = cm;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t u = s_cmax[0];
-#pragma unroll
-        for (int k = 1; k < kFsPruneThreads / 64; ++k) u = s_cmax[k] > u ? s_cmax[k] : u;
-        bcnt[blockIdx.x] = u;
-    }
+    const int32_t bc = fs_block_max(w);
+    if (threadIdx.x == 0) bcnt[blockIdx.x] = bc;
 }
 
 // fs_assoc_fold_kernel's count half alone: the largest count after the pass
 // goes to the host's coherent word
-__global__ __launch_bounds__(kFsPruneThreads) void fs_prune_fold_kernel(
+__global__ __launch_bounds__(kFsThreads) void fs_prune_fold_kernel(
     const int32_t* __restrict__ bcnt, const int32_t nb, int32_t* __restrict__ cmax_host) {
-    __shared__ int32_t s_cmax[kFsPruneThreads / 64];
     int32_t u = 0;
-    for (int32_t b = threadIdx.x; b < nb; b += kFsPruneThreads) u = bcnt[b] > u ? bcnt[b] : u;
-    u = fs_wave_max_i32(u);
-    if ((threadIdx.x & 63) == 0) s_cmax[threadIdx.x >> 6] = u;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u = s_cmax[0];
-#pragma unroll
-        for (int k = 1; k < kFsPruneThreads / 64; ++k) u = s_cmax[k] > u ? s_cmax[k] : u;
-        *cmax_host = u;
-    }
+    for (int32_t b = threadIdx.x; b < nb; b += kFsThreads) u = bcnt[b] > u ? bcnt[b] : u;
+    u = fs_block_max(u);
+    if (threadIdx.x == 0) *cmax_host = u;
 }
 
 // The evidence rows through the resampling indices, beside
 // fs_assoc_gather_kernel: particle p takes the rows of its source below the
 // source's own count (cnt_src: the counts before the gather).
-__global__ __launch_bounds__(kFsPruneThreads) void fs_prune_gather_kernel(
+__global__ __launch_bounds__(kFsThreads) void fs_prune_gather_kernel(
     const int64_t n, const int64_t npad, const int32_t* __restrict__ idx, const int32_t nrows,
     const int32_t* __restrict__ cnt_src, const int32_t* __restrict__ src,
     int32_t* __restrict__ dst) {
-    const int64_t p = (int64_t)blockIdx.x * kFsPruneThreads + threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * kFsThreads + threadIdx.x;
     if (p >= n) return;
     const int64_t q = idx[p];
     const int32_t cq = cnt_src[q];
@@ -148,18 +114,18 @@ void fs_prune_launch(hipStream_t stream, bool use_angle, int32_t nb, int64_t n, 
                      int32_t cap, const FsPrune& P, int32_t* ev, int32_t* removed, int32_t* bcnt,
                      int32_t* cmax_host) {
     if (use_angle)
-        fs_prune_kernel<true><<<nb, kFsPruneThreads, 0, stream>>>(
+        fs_prune_kernel<true><<<nb, kFsThreads, 0, stream>>>(
             n, npad, xs, ys, ts, map, cnt_io, cnt_before, stamp, call, cap, P, ev, removed, bcnt);
     else
-        fs_prune_kernel<false><<<nb, kFsPruneThreads, 0, stream>>>(
+        fs_prune_kernel<false><<<nb, kFsThreads, 0, stream>>>(
             n, npad, xs, ys, ts, map, cnt_io, cnt_before, stamp, call, cap, P, ev, removed, bcnt);
-    fs_prune_fold_kernel<<<1, kFsPruneThreads, 0, stream>>>(bcnt, nb, cmax_host);
+    fs_prune_fold_kernel<<<1, kFsThreads, 0, stream>>>(bcnt, nb, cmax_host);
 }
 
 void fs_prune_gather_launch(hipStream_t stream, dim3 grid, int64_t n, int64_t npad,
                             const int32_t* idx, int32_t nrows, const int32_t* cnt_src,
                             const int32_t* src, int32_t* dst) {
-    fs_prune_gather_kernel<<<grid, kFsPruneThreads, 0, stream>>>(n, npad, idx, nrows, cnt_src, src,
+    fs_prune_gather_kernel<<<grid, kFsThreads, 0, stream>>>(n, npad, idx, nrows, cnt_src, src,
                                                                  dst);
 }
 

@@ -6,11 +6,6 @@
 
 namespace slam {
 
-// the block size and the map's components per landmark: fastslam.inl's
-// kFsThreads and kFsComp (fs_api.inl asserts the equality)
-constexpr int kFsPruneThreads = 256;
-constexpr int kFsPruneComp = 5;
-
 struct FsPrune {
     double vr2, view_tan;       // view_range^2; in view iff ry >= |rx| view_tan (with the angle)
     int32_t init, hit, miss, ev_max, remove_below;
