@@ -1034,6 +1034,48 @@ int slam_graph_cond_info(slam_graph* h, double* out);
  * dense update, in the other modes, and when the estimate rejected H for
  * certain (cond_info status 2 / 4). */
 int slam_graph_gate_info(slam_graph* h, double* out);
+/* Joint marginal covariance of the poses at `times` (m distinct times of the
+ * current edge set): cov[3m][3m] row-major, block (a, b) = rows of times[a],
+ * columns of times[b] of H^-1.  relinearize = 1: H is linearised and assembled
+ * at the current poses first (the covariance belongs to what slam_graph_get_poses
+ * returns; slam_graph_get_system / get_bsr afterwards return this system);
+ * relinearize = 0: the last assembled system, i.e. the matrix updateEstPose
+ * inverted (:497).  info[6] = {is_calc, passes, max iterations of a column,
+ * worst final relative residual, device ms, columns per pass}.
+ *
+ * Arguments, checked on the host before any launch (SLAM_ERR_ARG): NULL
+ * pointers, m < 1, a time that is not among the edge set's times
+ * (slam_graph_get_system's `times`), a time given twice, relinearize = 0 with
+ * nothing assembled since the last slam_graph_set_edges, and a dense request
+ * above 2048 unknowns.  With no edges, or 3 n_times <= 3, is_calc = 0 as in
+ * slam_graph_update.  is_calc = 0 is not an error: the call returns SLAM_OK
+ * with cov filled with NaN, as slam_graph_update returns SLAM_OK with
+ * stats[0] = 0.
+ *
+ * Dense path (solver dense, or auto with n <= 2048): is_calc is the reference's
+ * gate det_min < det && cond < cond_max (:496) on this H, from the LU and
+ * Lanczos kernels of slam_graph_update; the 3m columns are substituted through
+ * that LU, one workgroup each (passes = 1, iterations and residual 0, columns
+ * per pass = 3m).
+ * PCG path: passes of up to `columns per pass` independent block-Jacobi
+ * preconditioned CGs on H x = e_j from x = 0; is_calc = 1 means every column
+ * converged to cfg.pcg_tol (relative residual) within cfg.pcg_max_iter with
+ * positive curvature; the call stops after the first pass that has a column
+ * which did not (max iterations = the cap then).  The eigenvalue estimate and
+ * the margin gate of slam_graph_update are NOT re-run: slam_graph_cond_info and
+ * slam_graph_gate_info still describe the last update.  A column's bits do not
+ * depend on what else is asked for, in which order, or on the columns per pass.
+ *
+ * The call does not move the poses and leaves slam_graph_get_delta,
+ * slam_graph_timing, cond_info, gate_info and the warm starts of the next
+ * update alone; its vectors are its own (allocated on first use, grow-only,
+ * released by slam_graph_destroy).  cov is not symmetrised: H is symmetric only
+ * to rounding (Omega = inv(...), :416), and so is its inverse. */
+int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t relinearize,
+                         double* cov, double* info);
+/* columns per pass of the PCG path: 1, 2, 4 or 8 (0: the default, 4);
+ * for A/B and tests */
+int slam_graph_set_marginal_cols(slam_graph* h, int32_t cols);
 /* HalfEdge (graph_based_slam.py:259-300) with its Observation (:20-75). */
 typedef struct {
     int64_t time, pose, landmark;

@@ -18,6 +18,7 @@
 #include "device_mem.hpp"
 #include "graph_kernels.inl"
 #include "graph_build.inl"
+#include "graph_marginals.inl"
 
 using namespace slam;
 
@@ -75,6 +76,15 @@ struct slam_graph {
     double last[5] = {0, 0, 0, 0, 0};
     int32_t pcg_last_iters = 0;    // iteration count of the previous PCG solve
     bool pcg_failed = false;       // the last update's PCG solve did not converge
+    bool assembled = false;        // val / b hold a system of the current edge set
+    // slam_graph_marginals: its own buffers (first use, grow-only) and events
+    DeviceMem marg;
+    char* marg_arena = nullptr;
+    size_t marg_bytes = 0;
+    MargState* marg_host = nullptr;  // pinned
+    hipEvent_t marg_ev[2] = {};
+    int32_t marg_cols = 0;         // columns per pass (0: kMargDefaultCols)
+    int32_t marg_last_iters = 0;   // iteration count of the previous pass (first batch length)
 };
 
 namespace {
@@ -421,8 +431,8 @@ int dense_matrix(slam_graph* h) {
     return SLAM_OK;
 }
 
-// dense path: det, cond, gate, delta (updateEstPose :494-502)
-int solve_dense(slam_graph* h, double* stats, bool* solved) {
+// dense path: LU of H and the reference's gate on it (updateEstPose :494-496)
+int dense_factor_gate(slam_graph* h, double* det_out, double* cond_out, bool* pass) {
     const int64_t n = 3 * h->nt;
     GTRY(dense_matrix(h));
     SLAM_HIP_TRY(hipMemcpyAsync(h->LU, h->A, n * n * sizeof(double), hipMemcpyDeviceToDevice,
@@ -441,9 +451,16 @@ int solve_dense(slam_graph* h, double* stats, bool* solved) {
     // numpy det: sign * exp(logdet); a zero pivot gives 0 (getrf info > 0)
     const double det = (lo[2] != 0.0) ? 0.0 : lo[0] * std::exp(lo[1]);
     const double cond = (lo[4] > 0.0) ? lo[3] / lo[4] : std::numeric_limits<double>::infinity();
-    stats[2] = det;
-    stats[3] = cond;
-    *solved = (h->cfg.det_min < det) && (cond < h->cfg.cond_max);
+    *det_out = det;
+    *cond_out = cond;
+    *pass = (h->cfg.det_min < det) && (cond < h->cfg.cond_max);
+    return SLAM_OK;
+}
+
+// dense path: det, cond, gate, delta (updateEstPose :494-502)
+int solve_dense(slam_graph* h, double* stats, bool* solved) {
+    const int64_t n = 3 * h->nt;
+    GTRY(dense_factor_gate(h, &stats[2], &stats[3], solved));
     if (*solved)
         hipLaunchKernelGGL(graph_lu_solve_kernel, dim3(1), dim3(kGraphThreads), 0, h->stream,
                            h->LU, (int)n, h->piv, h->b, h->delta);
@@ -829,6 +846,7 @@ int do_update(slam_graph* h, double* stats) {
     h->pcg_failed = false;
     if (h->E == 0 || 3 * h->nt <= 3) return SLAM_OK;        // :469 (leng > 3)
     GTRY(linearize_assemble(h));
+    h->assembled = true;
     const int64_t n = 3 * h->nt;
     const bool dense = (h->cfg.solver == SLAM_GRAPH_DENSE) ||
                        (h->cfg.solver == SLAM_GRAPH_AUTO && n <= kGraphDenseMax);
@@ -857,6 +875,166 @@ int do_update(slam_graph* h, double* stats) {
         h->last[k] = ms;
     }
     h->last[4] = iters;
+    return SLAM_OK;
+}
+
+// ---- slam_graph_marginals (graph_marginals.inl)
+constexpr int kMargDefaultCols = 4;     // least time per column at config 5
+constexpr int kMargWidths[] = {1, 2, 4, 8};
+static_assert(kMargDefaultCols <= kMargMaxCols, "MargState holds the widest pass");
+
+// the call's device buffers, carved from one grow-only allocation of h->marg
+struct MargBuffers {
+    double *minv, *x, *r, *z, *p, *q, *part, *tot, *cov;
+    int64_t* qidx;
+    MargState* st;
+};
+
+int marg_buffers(slam_graph* h, int64_t M, bool pcg, int cols, MargBuffers* mb) {
+    const int64_t n = 3 * h->nt;
+    const int64_t nv = pcg ? n * cols : 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        Carver c{pass ? h->marg_arena : nullptr};
+        mb->cov = c.take<double>(M * M);
+        mb->qidx = c.take<int64_t>(M);
+        mb->st = c.take<MargState>(1);
+        mb->minv = c.take<double>(pcg ? 9 * h->nt : 0);
+        mb->x = c.take<double>(nv);
+        mb->r = c.take<double>(nv);
+        mb->z = c.take<double>(nv);
+        mb->p = c.take<double>(nv);
+        mb->q = c.take<double>(nv);
+        mb->part = c.take<double>(pcg ? 3 * (int64_t)nblk(n, kPcgThreads) * cols : 0);
+        mb->tot = c.take<double>(3 * kMargMaxCols);
+        if (pass == 0 && c.off > h->marg_bytes) {
+            h->marg.release(h->marg_arena);
+            h->marg_bytes = 0;
+            GTRY(h->marg.alloc(&h->marg_arena, c.off));
+            h->marg_bytes = c.off;
+        }
+    }
+    if (!h->marg_host) {
+        GTRY(h->marg.alloc_pinned(&h->marg_host, nullptr, 1, hipHostMallocDefault));
+        for (auto& e : h->marg_ev) GTRY(h->marg.event(&e));
+    }
+    return SLAM_OK;
+}
+
+template <int W>
+void marg_start(slam_graph* h, const MargBuffers& mb, int64_t j0, int64_t M) {
+    const int64_t n = 3 * h->nt;
+    hipLaunchKernelGGL(graph_marg_start_kernel<W>, dim3(nblk(n, kPcgThreads)), dim3(kPcgThreads), 0,
+                       h->stream, n, mb.minv, mb.qidx, j0, M, mb.x, mb.r, mb.z, mb.part, mb.st);
+}
+
+// redundant folds (default): two launches per iteration; fold_launch: the
+// partials folded by a one-workgroup launch before each of them (four launches,
+// the same bits; SLAM_GRAPH_MARG_FOLD=1, measured and not kept: DESIGN 8.2)
+template <int W>
+void marg_iterations(slam_graph* h, const MargBuffers& mb, int32_t k0, int32_t k1, bool fold_launch) {
+    const int64_t n = 3 * h->nt;
+    const unsigned nb = nblk(n, kPcgThreads);
+    hipStream_t s = h->stream;
+    for (int32_t k = k0; k < k1; ++k) {
+        if (fold_launch) {
+            hipLaunchKernelGGL((graph_marg_fold_kernel<kSpmvThreads, W, 2>), dim3(1), dim3(kSpmvThreads),
+                               0, s, (int64_t)nb, mb.part, 1, mb.tot);
+            hipLaunchKernelGGL((graph_marg_dir_spmm_kernel<W, true>), dim3(nb), dim3(kSpmvThreads), 0, s,
+                               h->nt, k, h->rptr, h->scol, h->val, mb.z, mb.p, mb.q, mb.part, mb.tot,
+                               mb.st, h->cfg.pcg_tol, h->cfg.pcg_max_iter);
+            hipLaunchKernelGGL((graph_marg_fold_kernel<kPcgThreads, W, 1>), dim3(1), dim3(kPcgThreads),
+                               0, s, (int64_t)nb, mb.part, 0, mb.tot);
+            hipLaunchKernelGGL((graph_marg_step_kernel<W, true>), dim3(nb), dim3(kPcgThreads), 0, s, n,
+                               k, mb.minv, mb.p, mb.q, mb.x, mb.r, mb.z, mb.part, mb.tot, mb.st);
+        } else {
+            hipLaunchKernelGGL((graph_marg_dir_spmm_kernel<W, false>), dim3(nb), dim3(kSpmvThreads), 0, s,
+                               h->nt, k, h->rptr, h->scol, h->val, mb.z, mb.p, mb.q, mb.part, mb.tot,
+                               mb.st, h->cfg.pcg_tol, h->cfg.pcg_max_iter);
+            hipLaunchKernelGGL((graph_marg_step_kernel<W, false>), dim3(nb), dim3(kPcgThreads), 0, s, n,
+                               k, mb.minv, mb.p, mb.q, mb.x, mb.r, mb.z, mb.part, mb.tot, mb.st);
+        }
+    }
+}
+
+#define MARG_DISPATCH(W, fn, ...)                 \
+    switch (W) {                                  \
+        case 1: fn<1>(__VA_ARGS__); break;        \
+        case 2: fn<2>(__VA_ARGS__); break;        \
+        case 4: fn<4>(__VA_ARGS__); break;        \
+        default: fn<8>(__VA_ARGS__); break;       \
+    }
+
+// One pass of W columns (requests j0 .. j0 + W - 1, those past M padding) in the
+// manner of solve_pcg: enqueue a batch of iterations, poll a pinned copy of the
+// state.  The final state is left in *h->marg_host.
+int marg_pass(slam_graph* h, const MargBuffers& mb, int W, int64_t j0, int64_t M) {
+    MARG_DISPATCH(W, marg_start, h, mb, j0, M);
+    const char* fe = std::getenv("SLAM_GRAPH_MARG_FOLD");
+    const bool fold_launch = fe && fe[0] == '1';
+    const MargState& s = *h->marg_host;
+    int32_t k0 = 0;
+    int32_t k1 = std::max<int32_t>(16, std::min<int32_t>(h->marg_last_iters + 1, 1024));
+    for (;;) {
+        MARG_DISPATCH(W, marg_iterations, h, mb, k0, k1, fold_launch);
+        SLAM_HIP_TRY(hipGetLastError());
+        SLAM_HIP_TRY(hipMemcpyAsync(h->marg_host, mb.st, sizeof(MargState), hipMemcpyDeviceToHost,
+                                    h->stream));
+        SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+        if (s.done[0] || s.done[1]) break;
+        k0 = k1;
+        k1 += 16;
+    }
+    return SLAM_OK;
+}
+
+// the PCG path: passes of at most `cols` columns; a pass narrower than that runs
+// at the smallest instantiated width that holds it (the bits do not depend on
+// the width).  Stops at the first pass with a column that did not converge.
+int marg_pcg(slam_graph* h, const MargBuffers& mb, int64_t M, int cols, double* info) {
+    hipLaunchKernelGGL(graph_block_inv_kernel, dim3(nblk(h->nt)), dim3(256), 0, h->stream, h->nt,
+                       h->dslot, h->val, mb.minv);
+    bool ok = true;
+    int32_t passes = 0, max_iter = 0;
+    double worst = 0.0;
+    for (int64_t j0 = 0; j0 < M && ok; j0 += cols) {
+        int W = cols;
+        for (int w : kMargWidths)
+            if (w >= M - j0 && w < W) W = w;
+        GTRY(marg_pass(h, mb, W, j0, M));
+        ++passes;
+        const MargState& s = *h->marg_host;
+        int32_t pass_iter = 0;
+        for (int c = 0; c < W && j0 + c < M; ++c) {
+            ok = ok && s.status[c] == 1;
+            pass_iter = std::max(pass_iter, s.iter[c]);
+            const double rel = std::sqrt(s.rr[c] / s.rr0[c]);
+            if (!(rel <= worst)) worst = rel;      // a NaN residual is the worst
+        }
+        max_iter = std::max(max_iter, pass_iter);
+        h->marg_last_iters = ok ? pass_iter : 0;
+        hipLaunchKernelGGL(graph_marg_extract_kernel, dim3(nblk(M * W)), dim3(256), 0, h->stream, M, W,
+                           j0, mb.qidx, mb.x, mb.cov);
+        SLAM_HIP_TRY(hipGetLastError());
+    }
+    info[0] = ok ? 1.0 : 0.0;
+    info[1] = passes;
+    info[2] = max_iter;
+    info[3] = worst;
+    return SLAM_OK;
+}
+
+// the dense path: the reference's gate on this H, then one workgroup per column
+int marg_dense(slam_graph* h, const MargBuffers& mb, int64_t M, double* info) {
+    double det, cond;
+    bool pass = false;
+    GTRY(dense_factor_gate(h, &det, &cond, &pass));
+    if (pass) {
+        hipLaunchKernelGGL(graph_marg_lu_cols_kernel, dim3((unsigned)M), dim3(kMargDenseThreads), 0,
+                           h->stream, h->LU, (int)(3 * h->nt), h->piv, mb.qidx, M, mb.cov);
+        SLAM_HIP_TRY(hipGetLastError());
+    }
+    info[0] = pass ? 1.0 : 0.0;
+    info[1] = 1.0;
     return SLAM_OK;
 }
 
@@ -943,6 +1121,8 @@ int slam_graph_set_edges(slam_graph* h, int64_t n_edges, const slam_graph_edge* 
                        "slam_graph_set_edges: pose / time index out of range");
     }
     SLAM_HIP_TRY(hipSetDevice(h->device));
+    h->assembled = false;
+    h->marg_last_iters = 0;
     if (n_edges == 0) {
         h->E = h->nt = h->n_slots = 0;
         h->times_h.clear();
@@ -1052,6 +1232,81 @@ int slam_graph_cond_info(slam_graph* h, double* out) {
 int slam_graph_gate_info(slam_graph* h, double* out) {
     SLAM_ARG_CHECK(h && out, "slam_graph_gate_info: NULL argument");
     for (int k = 0; k < kGateInfo; ++k) out[k] = h->gate_info[k];
+    return SLAM_OK;
+}
+
+int slam_graph_set_marginal_cols(slam_graph* h, int32_t cols) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_marginal_cols: NULL handle");
+    bool known = cols == 0;
+    for (int w : kMargWidths) known = known || cols == w;
+    SLAM_ARG_CHECK(known, "slam_graph_set_marginal_cols: cols must be 0, 1, 2, 4 or 8");
+    h->marg_cols = cols;
+    return SLAM_OK;
+}
+
+int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t relinearize,
+                         double* cov, double* info) {
+    SLAM_ARG_CHECK(h && times && cov && info && m >= 1, "slam_graph_marginals: bad arguments");
+    SLAM_ARG_CHECK(h->poses, "slam_graph_marginals: set the poses first");
+    SLAM_ARG_CHECK(m <= (int64_t)1 << 20, "slam_graph_marginals: too many times");
+    const int64_t M = 3 * m;
+    const int cols = h->marg_cols ? h->marg_cols : kMargDefaultCols;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int k = 0; k < 6; ++k) info[k] = 0.0;
+    info[5] = cols;
+    if (h->E == 0 || 3 * h->nt <= 3) {                      // :469 (leng > 3), as do_update
+        std::fill(cov, cov + M * M, nan);
+        return SLAM_OK;
+    }
+    // times -> unknowns; distinct and all of the edge set, before any launch
+    std::vector<int64_t> qidx((size_t)M);
+    {
+        std::vector<int64_t> ranks((size_t)m);
+        for (int64_t a = 0; a < m; ++a) {
+            const auto it = std::lower_bound(h->times_h.begin(), h->times_h.end(), times[a]);
+            SLAM_ARG_CHECK(it != h->times_h.end() && *it == times[a],
+                           "slam_graph_marginals: a time that is not among the edge set's times");
+            ranks[a] = it - h->times_h.begin();
+            for (int q = 0; q < 3; ++q) qidx[3 * a + q] = 3 * ranks[a] + q;
+        }
+        std::sort(ranks.begin(), ranks.end());
+        SLAM_ARG_CHECK(std::adjacent_find(ranks.begin(), ranks.end()) == ranks.end(),
+                       "slam_graph_marginals: times must be distinct");
+    }
+    SLAM_ARG_CHECK(relinearize || h->assembled,
+                   "slam_graph_marginals: relinearize = 0 before any system was assembled");
+    const int64_t n = 3 * h->nt;
+    const bool dense = (h->cfg.solver == SLAM_GRAPH_DENSE) ||
+                       (h->cfg.solver == SLAM_GRAPH_AUTO && n <= kGraphDenseMax);
+    SLAM_ARG_CHECK(!dense || n <= kGraphDenseMax,
+                   "slam_graph_marginals: dense solver limited to 2048 unknowns");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    MargBuffers mb{};
+    GTRY(marg_buffers(h, M, !dense, cols, &mb));
+    hipStream_t s = h->stream;
+    SLAM_HIP_TRY(hipEventRecord(h->marg_ev[0], s));
+    if (relinearize) {
+        hipLaunchKernelGGL(graph_linearize_kernel, dim3(nblk(h->E)), dim3(256), 0, s, h->E, h->edges,
+                           h->poses, gconst(h->cfg), h->blocks);
+        hipLaunchKernelGGL(graph_assemble_h_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0, s,
+                           h->n_slots, h->E, h->cptr, h->clist, h->blocks, h->cfg.anchor, h->val);
+        hipLaunchKernelGGL(graph_assemble_b_kernel, dim3(nblk(3 * h->nt)), dim3(256), 0, s, h->nt,
+                           h->E, h->bptr, h->blist, h->blocks, h->b);
+        SLAM_HIP_TRY(hipGetLastError());
+        h->assembled = true;
+    }
+    SLAM_HIP_TRY(hipMemcpyAsync(mb.qidx, qidx.data(), M * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (dense) GTRY(marg_dense(h, mb, M, info));
+    else GTRY(marg_pcg(h, mb, M, cols, info));
+    SLAM_HIP_TRY(hipEventRecord(h->marg_ev[1], s));
+    if (info[0] != 0.0)
+        SLAM_HIP_TRY(hipMemcpyAsync(cov, mb.cov, M * M * sizeof(double), hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));      // qidx (host) is read by the upload until here
+    if (info[0] == 0.0) std::fill(cov, cov + M * M, nan);
+    float ms = 0.f;
+    SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->marg_ev[0], h->marg_ev[1]));
+    info[4] = ms;
+    if (dense) info[5] = (double)M;
     return SLAM_OK;
 }
 

@@ -8,7 +8,9 @@ ordered pair; ``updateEstPose`` linearises every pair at the current pose
 estimates, assembles H and b, applies the reference's gate and solves on the
 GPU (csrc/graph_kernels.inl), then writes the updated poses back into the
 caller's (3,1) arrays in place -- the reference mutates them in place too
-(:499-502), and its Robot relies on that aliasing.
+(:499-502), and its Robot relies on that aliasing.  ``getEstTrajCov`` (no
+reference counterpart) returns the estimated poses' marginal covariances, the
+diagonal blocks of the inv(H) the reference forms at :497.
 
 ``ScanSensor`` (:78-213) is the sensor simulator: ``scan(pose)`` (and
 ``scan_batch(poses)`` for many poses at once) computes the noise-free
@@ -237,6 +239,23 @@ class TrajectoryEstimator(object):
     def getEstTrajPose(self):
         return [p for p, o in zip(self._poses, self._is_obs) if o]
 
+    def getEstTrajCov(self, times=None):
+        """Marginal covariance of the estimated poses: {time: (3, 3)} for
+        ``times`` (default: every time of the last solved edge set, which the
+        device handle remembers), from H linearised at the final poses; None
+        when there is no solved edge set or H does not pass the gate.  The
+        reference forms inv(H) at :497 and keeps only the update."""
+        solved = self._dev.get_system(dense=False)[0].tolist() if self._dev.n_edges else []
+        if times is None:
+            times = solved
+        times = [int(t) for t in times]
+        if not times or len(solved) * 3 <= 3:
+            return None
+        is_calc, cov, _ = self._dev.marginals(times, relinearize=True)
+        if not is_calc:
+            return None
+        return {t: cov[k] for k, t in enumerate(times)}
+
     def _upload_poses(self):
         self._dev.set_poses(np.array([np.asarray(p, dtype=np.float64).reshape(3) for p in self._poses]))
 
@@ -361,11 +380,26 @@ class Robot(object):
     def getEstTrajPose(self):
         return self._est.getEstTrajPose()
 
+    def getEstTrajCov(self):
+        """{time: (3, 3)} marginal covariances of the estimated poses, or None
+        (TrajectoryEstimator.getEstTrajCov)."""
+        return self._est.getEstTrajCov()
+
     # ---------------------------------------------------------- drawing
-    def draw(self, aAx1, aAx2):
-        """:717-724: the world frame (ax1) and the robot frame (ax2)."""
+    def draw(self, aAx1, aAx2, ellipses=False):
+        """:717-724: the world frame (ax1) and the robot frame (ax2);
+        ``ellipses=True`` adds the position ellipses of the estimated poses."""
         self._draw_world(aAx1)
+        if ellipses:
+            self._draw_est_ellipses(aAx1)
         self._draw_robot_frame(aAx2)
+
+    def _draw_est_ellipses(self, ax):
+        from mylib import plots
+        covs = self.getEstTrajCov()
+        for t, cov in (covs or {}).items():
+            p = self._est._poses[t]
+            plots.error_ellipse(ax, (p[0, 0], p[1, 0]), self._ellipse, cov[0:2, 0:2])
 
     def _draw_track(self, ax, color, label, poses):
         from mylib import plots

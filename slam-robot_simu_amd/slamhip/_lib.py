@@ -293,6 +293,8 @@ SIGNATURES = {
     "slam_graph_timing": (C.c_int, [_P, _D]),
     "slam_graph_cond_info": (C.c_int, [_P, _D]),
     "slam_graph_gate_info": (C.c_int, [_P, _D]),
+    "slam_graph_marginals": (C.c_int, [_P, C.c_int64, _I64, C.c_int32, _D, _D]),
+    "slam_graph_set_marginal_cols": (C.c_int, [_P, C.c_int32]),
     "slam_graph_linearize_solve": (C.c_int, [C.POINTER(GraphConfig), _P, C.c_int64, _D, C.c_int64,
                                              _D, C.c_int]),
     "slam_graph_pair_halves": (C.c_int, [C.c_int64, _P, C.c_int64, C.c_int, _I64, _P]),

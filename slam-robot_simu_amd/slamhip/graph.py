@@ -166,6 +166,36 @@ class DeviceGraph:
                     lambda_max=out[3], iterations_min=int(out[4]), iterations_max=int(out[5]),
                     ms=out[6])
 
+    def marginals(self, times, relinearize=True, joint=False, symmetrize=True):
+        """Marginal covariances of the poses at ``times`` (distinct times of the
+        edge set): blocks of H^-1 (slam_graph_marginals).  ``relinearize=True``
+        linearises at the current poses first, ``False`` uses the system the
+        last update assembled.  Returns (is_calc, cov, info): cov is (m, 3, 3),
+        the diagonal blocks, or with ``joint=True`` the whole (3m, 3m) joint
+        covariance (block (a, b) = times[a] x times[b]); all NaN when is_calc is
+        False.  ``symmetrize`` averages the joint matrix with its transpose on
+        the host (H, and so its inverse, is symmetric only to rounding)."""
+        times = np.ascontiguousarray(times, dtype=np.int64).reshape(-1)
+        m = len(times)
+        cov = np.empty((3 * m, 3 * m))
+        out = np.zeros(6)
+        check(self._lib.slam_graph_marginals(self._h, m, times.ctypes.data_as(C.POINTER(C.c_int64)),
+                                             1 if relinearize else 0, dptr(cov), dptr(out)),
+              "slam_graph_marginals")
+        if symmetrize:
+            cov = 0.5 * (cov + cov.T)
+        if not joint:
+            cov = np.stack([cov[3 * a:3 * a + 3, 3 * a:3 * a + 3] for a in range(m)])
+        info = dict(passes=int(out[1]), iterations=int(out[2]), residual=out[3], ms=out[4],
+                    cols=int(out[5]))
+        return bool(out[0]), cov, info
+
+    def set_marginal_cols(self, cols):
+        """Columns per pass of the PCG path of ``marginals`` (1, 2, 4 or 8; 0:
+        the default).  The result's bits do not depend on it."""
+        check(self._lib.slam_graph_set_marginal_cols(self._h, int(cols)),
+              "slam_graph_set_marginal_cols")
+
     def gate_info(self):
         """The last PCG-path update's gate (cond="margin": an estimate with
         margins, not a certificate; slam_graph_gate_info): the log-det interval,
