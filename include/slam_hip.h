@@ -1076,6 +1076,50 @@ int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t
 /* columns per pass of the PCG path: 1, 2, 4 or 8 (0: the default, 4);
  * for A/B and tests */
 int slam_graph_set_marginal_cols(slam_graph* h, int32_t cols);
+/* Robust edge weights (no reference counterpart): iteratively
+ * re-weighted least squares inside the linearisation.  For edge e, with err and
+ * Omega as setPairObs forms them (:404-417), chi2_e = err^T Omega err; the
+ * weight w_e multiplies all six blocks and both right-hand-side parts of the
+ * edge, and is recomputed at every linearisation of the Gauss-Newton loop:
+ *   SLAM_GRAPH_ROBUST_NONE    w = 1                                    rho = chi2
+ *   SLAM_GRAPH_ROBUST_HUBER   w = 1 for chi2 <= k^2, else k/sqrt(chi2) rho = chi2, else 2k sqrt(chi2) - k^2
+ *   SLAM_GRAPH_ROBUST_CAUCHY  w = 1 / (1 + chi2/k^2)                   rho = k^2 ln(1 + chi2/k^2)
+ *   SLAM_GRAPH_ROBUST_DCS     w = s^2, s = min(1, 2P/(P + chi2))       rho = s^2 chi2 + P (1 - s)^2
+ * (param = k, or P for dcs).  chi2 = 0 gives w = 1 exactly.  The default is
+ * none: a handle on which slam_graph_set_robust is never called, or called
+ * with none, runs the unweighted kernel and computes bit for bit what it
+ * computed before the call existed.  Assembly, both solvers and the gate see
+ * the weighted blocks; slam_graph_marginals with relinearize = 1 on a robust
+ * handle therefore returns blocks of the inverse of the WEIGHTED H.  Above 2048
+ * unknowns SLAM_GRAPH_COND_MARGIN may leave the det half of the gate undecided
+ * on a weighted system (is_calc = 0, slam_graph_gate_info says so; measured at
+ * 50,000 poses): use SLAM_GRAPH_COND_ESTIMATE or _OFF there.
+ *
+ * slam_graph_set_robust: SLAM_ERR_ARG, checked on the host before anything
+ * else, for a NULL handle, an unknown kind, a non-finite param, and param <= 0
+ * with a kind other than none.  May be called at any time; takes effect at the
+ * next linearisation (slam_graph_update / optimize / marginals with
+ * relinearize = 1). */
+enum { SLAM_GRAPH_ROBUST_NONE = 0, SLAM_GRAPH_ROBUST_HUBER = 1, SLAM_GRAPH_ROBUST_CAUCHY = 2,
+       SLAM_GRAPH_ROBUST_DCS = 3 };
+int slam_graph_set_robust(slam_graph* h, int32_t kind, double param);
+/* Chi-square of the edge set at the current poses under the handle's kind (one
+ * lane per edge: err and Omega only, no Jacobians and no blocks).  totals[4] =
+ * {sum chi2, sum rho, max chi2, number of edges with w < 0.1}; chi2 and weight
+ * receive n_edges values each (or NULL).  The totals are folded in a fixed
+ * order: bit-identical from call to call.  The call moves nothing and leaves
+ * slam_graph_get_system, get_delta, timing, cond_info, gate_info and
+ * slam_graph_get_edge_weights alone.  With no edges it returns SLAM_OK with the
+ * totals zero.  SLAM_ERR_ARG for a NULL handle or NULL totals (checked before
+ * the handle is read; the outputs are not written). */
+int slam_graph_chi2(slam_graph* h, double* totals, double* chi2, double* weight);
+/* chi2_e and w_e as the last linearisation stored them (n_edges each, or NULL):
+ * the weights the last assembled H actually used, i.e. those at the poses
+ * BEFORE the update that linearised.  SLAM_ERR_ARG when nothing has been
+ * linearised since slam_graph_set_edges, and when that linearisation ran with
+ * kind none: the unweighted kernel stores no rows (every weight was 1), and
+ * the poses it ran at are gone after the update -- use slam_graph_chi2. */
+int slam_graph_get_edge_weights(slam_graph* h, double* chi2, double* weight);
 /* HalfEdge (graph_based_slam.py:259-300) with its Observation (:20-75). */
 typedef struct {
     int64_t time, pose, landmark;

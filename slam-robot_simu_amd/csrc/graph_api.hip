@@ -85,6 +85,15 @@ struct slam_graph {
     hipEvent_t marg_ev[2] = {};
     int32_t marg_cols = 0;         // columns per pass (0: kMargDefaultCols)
     int32_t marg_last_iters = 0;   // iteration count of the previous pass (first batch length)
+    // robust edge weights (slam_graph_set_robust): their own array
+    // (first use, grow-only): [2][cap] rows (chi2, w) of the last linearisation,
+    // [2][cap] of the last slam_graph_chi2, its partials and totals
+    int32_t robust_kind = SLAM_GRAPH_ROBUST_NONE;
+    double robust_param = 0.0;
+    int32_t lin_kind = -1;         // kind of the last linearisation (-1: none since set_edges)
+    DeviceMem robust;
+    double* rw = nullptr;
+    int64_t rw_cap = 0;            // edges rw was sized for
 };
 
 namespace {
@@ -407,10 +416,75 @@ int build_structure(slam_graph* h, int64_t E, const slam_graph_edge* ed) {
 
 GraphConst gconst(const slam_graph_config& c) { return GraphConst{c.r_dist, c.r_dir, c.r_orient}; }
 
+// the robust array's parts for E edges
+struct RobustRows {
+    double *lin, *eval, *part, *tot;
+};
+
+RobustRows robust_rows(const slam_graph* h) {
+    const int64_t cap = h->rw_cap;
+    return RobustRows{h->rw, h->rw + 2 * cap, h->rw + 4 * cap,
+                      h->rw + 4 * cap + 4 * (int64_t)nblk(cap, kChi2Threads)};
+}
+
+int robust_reserve(slam_graph* h) {
+    if (h->rw && h->E <= h->rw_cap) return SLAM_OK;
+    h->robust.release(h->rw);
+    h->rw_cap = 0;
+    const int64_t cap = h->E + h->E / 4;
+    GTRY(h->robust.alloc(&h->rw, (size_t)(4 * cap + 4 * (int64_t)nblk(cap, kChi2Threads) + 4)));
+    h->rw_cap = cap;
+    return SLAM_OK;
+}
+
+// the linearise launch of both sites (linearize_assemble, slam_graph_marginals)
+// with the handle's robust kind; a none handle takes the unweighted
+// instantiation and never allocates the rows
+int launch_linearize(slam_graph* h) {
+    const int32_t kind = h->robust_kind;
+    double* rows = nullptr;
+    if (kind != SLAM_GRAPH_ROBUST_NONE) {
+        GTRY(robust_reserve(h));
+        rows = robust_rows(h).lin;
+    }
+#define SLAM_LINEARIZE(K)                                                                         \
+    hipLaunchKernelGGL(graph_linearize_kernel<K>, dim3(nblk(h->E)), dim3(256), 0, h->stream, h->E, \
+                       h->edges, h->poses, gconst(h->cfg), h->blocks, h->robust_param, rows)
+    switch (kind) {
+        case SLAM_GRAPH_ROBUST_HUBER: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_HUBER); break;
+        case SLAM_GRAPH_ROBUST_CAUCHY: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_CAUCHY); break;
+        case SLAM_GRAPH_ROBUST_DCS: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_DCS); break;
+        default: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_NONE); break;      // set_robust admits no other
+    }
+#undef SLAM_LINEARIZE
+    h->lin_kind = kind;
+    return SLAM_OK;
+}
+
+// chi2_e, w_e of every edge at the current poses into `rows` ([2][E]) and the
+// four totals into the robust array (graph_chi2_kernel, then its fold)
+int launch_chi2(slam_graph* h, double* rows) {
+    const RobustRows r = robust_rows(h);
+    const unsigned nb = nblk(h->E, kChi2Threads);
+#define SLAM_CHI2(K)                                                                               \
+    hipLaunchKernelGGL(graph_chi2_kernel<K>, dim3(nb), dim3(kChi2Threads), 0, h->stream, h->E,     \
+                       h->edges, h->poses, gconst(h->cfg), h->robust_param, rows, r.part)
+    switch (h->robust_kind) {
+        case SLAM_GRAPH_ROBUST_HUBER: SLAM_CHI2(SLAM_GRAPH_ROBUST_HUBER); break;
+        case SLAM_GRAPH_ROBUST_CAUCHY: SLAM_CHI2(SLAM_GRAPH_ROBUST_CAUCHY); break;
+        case SLAM_GRAPH_ROBUST_DCS: SLAM_CHI2(SLAM_GRAPH_ROBUST_DCS); break;
+        default: SLAM_CHI2(SLAM_GRAPH_ROBUST_NONE); break;
+    }
+#undef SLAM_CHI2
+    hipLaunchKernelGGL(graph_chi2_fold_kernel, dim3(1), dim3(kChi2FoldThreads), 0, h->stream,
+                       (int64_t)nb, r.part, r.tot);
+    SLAM_HIP_TRY(hipGetLastError());
+    return SLAM_OK;
+}
+
 int linearize_assemble(slam_graph* h) {
     SLAM_HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    hipLaunchKernelGGL(graph_linearize_kernel, dim3(nblk(h->E)), dim3(256), 0, h->stream, h->E,
-                       h->edges, h->poses, gconst(h->cfg), h->blocks);
+    GTRY(launch_linearize(h));
     SLAM_HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     hipLaunchKernelGGL(graph_assemble_h_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0,
                        h->stream, h->n_slots, h->E, h->cptr, h->clist, h->blocks, h->cfg.anchor,
@@ -1123,6 +1197,7 @@ int slam_graph_set_edges(slam_graph* h, int64_t n_edges, const slam_graph_edge* 
     SLAM_HIP_TRY(hipSetDevice(h->device));
     h->assembled = false;
     h->marg_last_iters = 0;
+    h->lin_kind = -1;
     if (n_edges == 0) {
         h->E = h->nt = h->n_slots = 0;
         h->times_h.clear();
@@ -1286,8 +1361,7 @@ int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t
     hipStream_t s = h->stream;
     SLAM_HIP_TRY(hipEventRecord(h->marg_ev[0], s));
     if (relinearize) {
-        hipLaunchKernelGGL(graph_linearize_kernel, dim3(nblk(h->E)), dim3(256), 0, s, h->E, h->edges,
-                           h->poses, gconst(h->cfg), h->blocks);
+        GTRY(launch_linearize(h));      // the handle's robust kind: the weighted H
         hipLaunchKernelGGL(graph_assemble_h_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0, s,
                            h->n_slots, h->E, h->cptr, h->clist, h->blocks, h->cfg.anchor, h->val);
         hipLaunchKernelGGL(graph_assemble_b_kernel, dim3(nblk(3 * h->nt)), dim3(256), 0, s, h->nt,
@@ -1307,6 +1381,53 @@ int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t
     SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->marg_ev[0], h->marg_ev[1]));
     info[4] = ms;
     if (dense) info[5] = (double)M;
+    return SLAM_OK;
+}
+
+int slam_graph_set_robust(slam_graph* h, int32_t kind, double param) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_robust: NULL handle");
+    SLAM_ARG_CHECK(kind == SLAM_GRAPH_ROBUST_NONE || kind == SLAM_GRAPH_ROBUST_HUBER ||
+                       kind == SLAM_GRAPH_ROBUST_CAUCHY || kind == SLAM_GRAPH_ROBUST_DCS,
+                   "slam_graph_set_robust: unknown kind");
+    SLAM_ARG_CHECK(std::isfinite(param), "slam_graph_set_robust: the parameter is not finite");
+    SLAM_ARG_CHECK(kind == SLAM_GRAPH_ROBUST_NONE || param > 0.0,
+                   "slam_graph_set_robust: the parameter of huber, cauchy and dcs must be > 0");
+    h->robust_kind = kind;
+    h->robust_param = param;
+    return SLAM_OK;
+}
+
+int slam_graph_chi2(slam_graph* h, double* totals, double* chi2, double* weight) {
+    SLAM_ARG_CHECK(h && totals, "slam_graph_chi2: NULL handle or totals");
+    for (int k = 0; k < 4; ++k) totals[k] = 0.0;
+    if (h->E == 0) return SLAM_OK;
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    GTRY(robust_reserve(h));
+    const RobustRows r = robust_rows(h);
+    GTRY(launch_chi2(h, r.eval));
+    hipStream_t s = h->stream;
+    const size_t row = (size_t)h->E * sizeof(double);
+    SLAM_HIP_TRY(hipMemcpyAsync(totals, r.tot, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (chi2) SLAM_HIP_TRY(hipMemcpyAsync(chi2, r.eval, row, hipMemcpyDeviceToHost, s));
+    if (weight) SLAM_HIP_TRY(hipMemcpyAsync(weight, r.eval + h->E, row, hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
+    return SLAM_OK;
+}
+
+int slam_graph_get_edge_weights(slam_graph* h, double* chi2, double* weight) {
+    SLAM_ARG_CHECK(h, "slam_graph_get_edge_weights: NULL handle");
+    SLAM_ARG_CHECK(h->lin_kind >= 0,
+                   "slam_graph_get_edge_weights: nothing linearised since slam_graph_set_edges");
+    SLAM_ARG_CHECK(h->lin_kind != SLAM_GRAPH_ROBUST_NONE,
+                   "slam_graph_get_edge_weights: the last linearisation ran with kind none and "
+                   "stored no rows (every weight was 1; slam_graph_chi2 evaluates chi2)");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    const RobustRows r = robust_rows(h);
+    hipStream_t s = h->stream;
+    const size_t row = (size_t)h->E * sizeof(double);
+    if (chi2) SLAM_HIP_TRY(hipMemcpyAsync(chi2, r.lin, row, hipMemcpyDeviceToHost, s));
+    if (weight) SLAM_HIP_TRY(hipMemcpyAsync(weight, r.lin + h->E, row, hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
     return SLAM_OK;
 }
 

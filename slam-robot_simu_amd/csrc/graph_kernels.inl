@@ -115,18 +115,12 @@ __device__ __forceinline__ void inv3_lu(const double* S, double* X) {
     }
 }
 
-// One lane per edge: setPairObs (:362-439).  blocks: SoA [42][E] = BB, BA, AB,
-// AA (row-major 3x3), b_B, b_A.
-__global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
-                                                              const slam_graph_edge* __restrict__ edges,
-                                                              const double* __restrict__ poses,
-                                                              const GraphConst g,
-                                                              double* __restrict__ blocks) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const slam_graph_edge ed = edges[e];
-    const double* xb = poses + 3 * ed.pose_bfr;
-    const double* xa = poses + 3 * ed.pose_aft;
+// err (:517-581) and the information matrix Omega (:410-417) of one edge at the
+// current estimates: the one statement of both, shared by the linearise and
+// the chi-square kernels.
+__device__ __forceinline__ void edge_err_info(const slam_graph_edge& ed, const double* xb,
+                                              const double* xa, const GraphConst& g, double* err,
+                                              double* W) {
     const double db = ed.obs_bfr[0], ab = ed.obs_bfr[1], ob = ed.obs_bfr[2];
     const double da = ed.obs_aft[0], aa = ed.obs_aft[1], oa = ed.obs_aft[2];
     // relative pose from the estimates (:517-537)
@@ -141,14 +135,95 @@ __global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
     const double px = da * ca - db * cb;
     const double py = da * sa - db * sb;
     const double pt = wrap_angle(la2 - lb2);
-    const double err[3] = {rx - px, ry - py, wrap_angle(rt - pt)};
+    err[0] = rx - px;
+    err[1] = ry - py;
+    err[2] = wrap_angle(rt - pt);
     // information matrix (:410-417)
-    double Ca[9], Cb[9], S[9], W[9];
+    double Ca[9], Cb[9], S[9];
     meas_cov_world(da, aa, xa[2], g, Ca);
     meas_cov_world(db, ab, xb[2], g, Cb);
 #pragma unroll
     for (int q = 0; q < 9; ++q) S[q] = Ca[q] + Cb[q];
     inv3_lu(S, W);
+}
+
+// Robust edge weights (SLAM_GRAPH_ROBUST_* of slam_hip.h).  For
+// chi2 = err^T Omega err the weight w multiplies the edge's six blocks and both
+// right-hand-side parts (iteratively re-weighted least squares), rho is the
+// robust cost:
+//   none       w = 1                                      rho = chi2
+//   huber(k)   w = 1 (chi2 <= k^2), else k / sqrt(chi2)   rho = chi2, else 2 k sqrt(chi2) - k^2
+//   cauchy(k)  w = 1 / (1 + chi2 / k^2)                   rho = k^2 ln(1 + chi2 / k^2)
+//   dcs(Phi)   w = s^2, s = min(1, 2 Phi / (Phi + chi2))  rho = s^2 chi2 + Phi (1 - s)^2
+// All three are continuous in chi2, and chi2 = 0 gives w = 1 exactly.
+__device__ __forceinline__ double edge_chi2(const double* err, const double* W) {
+    double t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double acc = W[3 * i] * err[0];
+        acc = fma(W[3 * i + 1], err[1], acc);
+        t[i] = fma(W[3 * i + 2], err[2], acc);
+    }
+    double c = err[0] * t[0];
+    c = fma(err[1], t[1], c);
+    return fma(err[2], t[2], c);
+}
+
+template <int KIND>
+__device__ __forceinline__ void robust_weight(const double chi2, const double param, double& w,
+                                              double& rho) {
+    if constexpr (KIND == SLAM_GRAPH_ROBUST_HUBER) {
+        if (chi2 <= param * param) {
+            w = 1.0;
+            rho = chi2;
+        } else {
+            const double r = sqrt(chi2);
+            w = param / r;
+            rho = 2.0 * param * r - param * param;
+        }
+    } else if constexpr (KIND == SLAM_GRAPH_ROBUST_CAUCHY) {
+        const double t = 1.0 + chi2 / (param * param);
+        w = 1.0 / t;
+        rho = param * param * log(t);
+    } else if constexpr (KIND == SLAM_GRAPH_ROBUST_DCS) {
+        const double s = fmin(1.0, 2.0 * param / (param + chi2));
+        w = s * s;
+        rho = s * s * chi2 + param * (1.0 - s) * (1.0 - s);
+    } else {
+        w = 1.0;
+        rho = chi2;
+    }
+}
+
+// One lane per edge: setPairObs (:362-439).  blocks: SoA [42][E] = BB, BA, AB,
+// AA (row-major 3x3), b_B, b_A.  KIND != none: every one of the 42 values is
+// multiplied by the edge's weight, and rows ([2][E]: chi2, w) receives what the
+// weight came from; the none instantiation reads neither param nor rows.
+template <int KIND>
+__global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
+                                                              const slam_graph_edge* __restrict__ edges,
+                                                              const double* __restrict__ poses,
+                                                              const GraphConst g,
+                                                              double* __restrict__ blocks,
+                                                              const double param,
+                                                              double* __restrict__ rows) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const slam_graph_edge ed = edges[e];
+    const double* xb = poses + 3 * ed.pose_bfr;
+    const double* xa = poses + 3 * ed.pose_aft;
+    const double db = ed.obs_bfr[0], ab = ed.obs_bfr[1];
+    const double da = ed.obs_aft[0], aa = ed.obs_aft[1];
+    double err[3], W[9];
+    edge_err_info(ed, xb, xa, g, err, W);
+    double w = 1.0;
+    if constexpr (KIND != SLAM_GRAPH_ROBUST_NONE) {
+        const double chi2 = edge_chi2(err, W);
+        double rho;
+        robust_weight<KIND>(chi2, param, w, rho);
+        rows[e] = chi2;
+        rows[E + e] = w;
+    }
     // Jacobians (:420-427)
     double st, ct;
     sincos(wrap_angle(xb[2] + ab), &st, &ct);
@@ -156,28 +231,34 @@ __global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
     sincos(wrap_angle(xa[2] + aa), &st, &ct);
     const double Ja[9] = {1.0, 0.0, -da * st, 0.0, 1.0, da * ct, 0.0, 0.0, 1.0};
     double JbW[9], JaW[9], out[9];
+    // the weight is applied to the stored value only (x * 1.0 = x: an edge with
+    // w = 1 stores the bits of the none instantiation)
+    auto put = [&](const int row, const double v) {
+        if constexpr (KIND != SLAM_GRAPH_ROBUST_NONE) blocks[(int64_t)row * E + e] = v * w;
+        else blocks[(int64_t)row * E + e] = v;
+    };
     mat3_tmul(Jb, W, JbW);
     mat3_tmul(Ja, W, JaW);
     mat3_mul(JbW, Jb, out);
 #pragma unroll
-    for (int q = 0; q < 9; ++q) blocks[(int64_t)q * E + e] = out[q];
+    for (int q = 0; q < 9; ++q) put(q, out[q]);
     mat3_mul(JbW, Ja, out);
 #pragma unroll
-    for (int q = 0; q < 9; ++q) blocks[(int64_t)(9 + q) * E + e] = out[q];
+    for (int q = 0; q < 9; ++q) put(9 + q, out[q]);
     mat3_mul(JaW, Jb, out);
 #pragma unroll
-    for (int q = 0; q < 9; ++q) blocks[(int64_t)(18 + q) * E + e] = out[q];
+    for (int q = 0; q < 9; ++q) put(18 + q, out[q]);
     mat3_mul(JaW, Ja, out);
 #pragma unroll
-    for (int q = 0; q < 9; ++q) blocks[(int64_t)(27 + q) * E + e] = out[q];
+    for (int q = 0; q < 9; ++q) put(27 + q, out[q]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         double acc = JbW[3 * i] * err[0];
         acc = fma(JbW[3 * i + 1], err[1], acc);
-        blocks[(int64_t)(36 + i) * E + e] = fma(JbW[3 * i + 2], err[2], acc);
+        put(36 + i, fma(JbW[3 * i + 2], err[2], acc));
         acc = JaW[3 * i] * err[0];
         acc = fma(JaW[3 * i + 1], err[1], acc);
-        blocks[(int64_t)(39 + i) * E + e] = fma(JaW[3 * i + 2], err[2], acc);
+        put(39 + i, fma(JaW[3 * i + 2], err[2], acc));
     }
 }
 
@@ -1606,6 +1687,71 @@ __global__ __launch_bounds__(kCertThreads) void graph_cert_fold_kernel(
         out->trm_max = trm;
         out->trminv_max = tri;
         out->bad = (int32_t)bad;
+    }
+}
+
+// ------------------------------------------- chi-square of the edge set
+// slam_graph_chi2.  One lane per edge: err and Omega from
+// edge_err_info (no Jacobians, none of the 42 block stores), chi2_e and w_e to
+// rows ([2][E]), and the workgroup's partials to part: [0, nb) sum chi2,
+// [nb, 2nb) sum rho, [2nb, 3nb) max chi2, [3nb, 4nb) edges with w < 0.1.  A
+// workgroup covers kChi2Threads edges whatever the grid; graph_chi2_fold_kernel
+// (one workgroup) folds the partials as pcg_fold does -- each lane its strided
+// partials in order, then the fixed tree -- so the totals depend on E alone.
+constexpr int kChi2Threads = 128;
+constexpr int kChi2FoldThreads = 256;
+constexpr double kChi2LowWeight = 0.1;
+
+template <int KIND>
+__global__ __launch_bounds__(kChi2Threads) void graph_chi2_kernel(
+    const int64_t E, const slam_graph_edge* __restrict__ edges, const double* __restrict__ poses,
+    const GraphConst g, const double param, double* __restrict__ rows, double* __restrict__ part) {
+    __shared__ double sh[3 * kChi2Threads / 64];
+    const int64_t nb = gridDim.x;
+    const int64_t e = (int64_t)blockIdx.x * kChi2Threads + threadIdx.x;
+    double v[3] = {0.0, 0.0, 0.0};      // chi2, rho, low-weight count
+    double mx = -__builtin_huge_val();
+    if (e < E) {
+        const slam_graph_edge ed = edges[e];
+        double err[3], W[9];
+        edge_err_info(ed, poses + 3 * ed.pose_bfr, poses + 3 * ed.pose_aft, g, err, W);
+        const double chi2 = edge_chi2(err, W);
+        double w, rho;
+        robust_weight<KIND>(chi2, param, w, rho);
+        rows[e] = chi2;
+        rows[E + e] = w;
+        v[0] = chi2;
+        v[1] = rho;
+        v[2] = (w < kChi2LowWeight) ? 1.0 : 0.0;
+        mx = chi2;
+    }
+    block_sumK_fixed<kChi2Threads, 3>(v, sh);
+    mx = block_max_fixed<kChi2Threads>(mx, sh);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = v[0];
+        part[nb + blockIdx.x] = v[1];
+        part[2 * nb + blockIdx.x] = mx;
+        part[3 * nb + blockIdx.x] = v[2];
+    }
+}
+
+// tot[4] = {sum chi2, sum rho, max chi2, edges with w < 0.1}
+__global__ __launch_bounds__(kChi2FoldThreads) void graph_chi2_fold_kernel(
+    const int64_t nb, const double* __restrict__ part, double* __restrict__ tot) {
+    __shared__ double sh[3 * kChi2FoldThreads / 64];
+    double v[3];
+    v[0] = pcg_fold_lane<kChi2FoldThreads>(part, nb);
+    v[1] = pcg_fold_lane<kChi2FoldThreads>(part + nb, nb);
+    v[2] = pcg_fold_lane<kChi2FoldThreads>(part + 3 * nb, nb);
+    double mx = -__builtin_huge_val();
+    for (int64_t k = threadIdx.x; k < nb; k += kChi2FoldThreads) mx = fmax(mx, part[2 * nb + k]);
+    block_sumK_fixed<kChi2FoldThreads, 3>(v, sh);
+    mx = block_max_fixed<kChi2FoldThreads>(mx, sh);
+    if (threadIdx.x == 0) {
+        tot[0] = v[0];
+        tot[1] = v[1];
+        tot[2] = mx;
+        tot[3] = v[2];
     }
 }
 

@@ -209,14 +209,15 @@ def _rec_row(r):
 class TrajectoryEstimator(object):
     """Pose-graph estimator (GPU linearise / assemble / solve)."""
 
-    def __init__(self, aPose, *, solver="auto", device=0):
+    def __init__(self, aPose, *, solver="auto", device=0, robust=None):
         self._poses = [aPose]
         self._is_obs = [True]
         self._rows = []
         self._lm_ids = []
         self._times = []
         self._device = device
-        self._dev = DeviceGraph(solver=solver, device=device)
+        self._pairs = None          # the pair list estimate_trajectory last handed to the device
+        self._dev = DeviceGraph(solver=solver, device=device, robust=robust)
 
     def addPose(self, aPose, aIsObs):
         self._poses.append(aPose)
@@ -255,6 +256,20 @@ class TrajectoryEstimator(object):
         if not is_calc:
             return None
         return {t: cov[k] for k, t in enumerate(times)}
+
+    def getEdgeWeights(self):
+        """(pairs, chi2, weight) of the last ``estimate_trajectory`` on an
+        estimator made with ``robust=(kind, param)``: ``pairs`` are the
+        slam_graph_edge records in the order of the pair list that call built,
+        chi2 and weight what the last linearisation of the Gauss-Newton loop
+        stored for each -- the weights the last solved H used, so a pair with a
+        small weight is a pairing the optimiser rejected.  None before any
+        ``estimate_trajectory`` reached the device; on an estimator without a
+        robust kind the device call raises (no weights are stored)."""
+        if self._pairs is None:
+            return None
+        chi2, weight = self._dev.edge_weights()
+        return self._pairs, chi2, weight
 
     def _upload_poses(self):
         self._dev.set_poses(np.array([np.asarray(p, dtype=np.float64).reshape(3) for p in self._poses]))
@@ -307,6 +322,7 @@ class TrajectoryEstimator(object):
         # iteration 1 (:697-706): pairs set before this call -- linearised at
         # their setPairObs time, i.e. at these same poses -- plus this pairing
         self._dev.set_edges(first)
+        self._pairs = first
         st = [self._dev.update()]
         self._write_back(sorted(self._times))
         self._rows, self._lm_ids, self._times = [], [], []
@@ -315,6 +331,7 @@ class TrajectoryEstimator(object):
         if DELTA_SUM_TH <= st[0][1] and max_iter > 1 and len(paired):
             if pending is not None:
                 self._dev.set_edges(paired)
+                self._pairs = paired
             st += list(self._dev.optimize(DELTA_SUM_TH, max_iter - 1))
             self._write_back(times_of(paired))
         return np.array(st, dtype=np.float64).reshape(-1, 4)
@@ -328,13 +345,13 @@ class Robot(object):
 
     DELTA_SUM_TH = 0.01                                       # :630
 
-    def __init__(self, aPose, aDt, aScanRng_m, aScanAng_rad, aLandMarks, *, device=0):
+    def __init__(self, aPose, aDt, aScanRng_m, aScanAng_rad, aLandMarks, *, device=0, robust=None):
         from mylib.error_ellipse import ErrorEllipse
         from motion_model import MotionModel
         self._sensor = ScanSensor(aScanRng_m, aScanAng_rad, aLandMarks, device=device)
         self._sensor.setNoiseParam(5, 2, 2)                   # :604
         self._motion = MotionModel(aDt, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, device=device)
-        self._est = TrajectoryEstimator(aPose, device=device)
+        self._est = TrajectoryEstimator(aPose, device=device, robust=robust)
         self._dt = aDt
         self._time = 0
         self._poses = [aPose]                                 # actual poses

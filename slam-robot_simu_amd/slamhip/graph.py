@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import GRAPH_COND, GRAPH_SOLVER, GraphConfig, check, dptr
+from ._lib import GRAPH_COND, GRAPH_ROBUST, GRAPH_SOLVER, GraphConfig, check, dptr
 
 # slam_graph_edge, 80 bytes
 EDGE_DTYPE = np.dtype([("time_bfr", "<i8"), ("pose_bfr", "<i8"), ("time_aft", "<i8"),
@@ -65,7 +65,8 @@ class DeviceGraph:
 
     def __init__(self, *, r_dist=0.05, r_dir=np.deg2rad(2.0), r_orient=np.deg2rad(2.0),
                  anchor=1e4, det_min=0.1, cond_max=1e15, solver="auto", pcg_tol=1e-10,
-                 pcg_max_iter=20000, cond="margin", cond_tol=1e-5, cond_max_iter=3000, device=0):
+                 pcg_max_iter=20000, cond="margin", cond_tol=1e-5, cond_max_iter=3000, device=0,
+                 robust=None):
         cfg = GraphConfig()
         cfg.r_dist, cfg.r_dir, cfg.r_orient = float(r_dist), float(r_dir), float(r_orient)
         cfg.anchor, cfg.det_min, cfg.cond_max = float(anchor), float(det_min), float(cond_max)
@@ -80,6 +81,51 @@ class DeviceGraph:
         self._h = h
         self.n_poses = 0
         self.n_edges = 0
+        if robust is not None:
+            try:
+                self.set_robust(*robust)
+            except Exception:
+                self.close()
+                raise
+
+    def set_robust(self, kind, param=None):
+        """Robust edge weights (slam_graph_set_robust): ``kind`` is
+        None / "none", or "huber" / "cauchy" (``param`` = k) or "dcs" (``param``
+        = Phi).  Takes effect at the next linearisation.  Above 2048 unknowns
+        use ``cond="estimate"`` (or "off") with a robust kind: the margin gate's
+        det half may stay undecided on the weighted system."""
+        kind = "none" if kind is None else kind
+        if kind not in GRAPH_ROBUST:
+            raise ValueError("robust kind must be one of %s" % (sorted(GRAPH_ROBUST),))
+        if kind != "none" and param is None:
+            raise ValueError("robust kind %r needs its parameter" % (kind,))
+        check(self._lib.slam_graph_set_robust(self._h, GRAPH_ROBUST[kind],
+                                              0.0 if param is None else float(param)),
+              "slam_graph_set_robust")
+
+    def chi2(self, per_edge=False):
+        """Chi-square of the edge set at the current poses under the handle's
+        robust kind (slam_graph_chi2): dict(chi2=sum chi2_e, cost=sum rho_e,
+        max_chi2, n_low_weight=edges with w < 0.1), plus the per-edge arrays
+        ``edge_chi2`` and ``edge_weight`` with ``per_edge=True``.  Moves nothing."""
+        tot = np.zeros(4)
+        c = np.empty(self.n_edges) if per_edge else None
+        w = np.empty(self.n_edges) if per_edge else None
+        check(self._lib.slam_graph_chi2(self._h, dptr(tot), dptr(c), dptr(w)), "slam_graph_chi2")
+        out = dict(chi2=float(tot[0]), cost=float(tot[1]), max_chi2=float(tot[2]),
+                   n_low_weight=int(tot[3]))
+        if per_edge:
+            out["edge_chi2"], out["edge_weight"] = c, w
+        return out
+
+    def edge_weights(self):
+        """(chi2, weight) per edge as the last linearisation stored them: the
+        weights the last assembled H used (slam_graph_get_edge_weights; an
+        error on a handle whose last linearisation ran without a robust kind)."""
+        c, w = np.empty(self.n_edges), np.empty(self.n_edges)
+        check(self._lib.slam_graph_get_edge_weights(self._h, dptr(c), dptr(w)),
+              "slam_graph_get_edge_weights")
+        return c, w
 
     def close(self):
         if getattr(self, "_h", None):
