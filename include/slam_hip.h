@@ -986,6 +986,42 @@ int slam_graph_set_poses(slam_graph* h, int64_t n_poses, const double* poses);
 int slam_graph_get_poses(slam_graph* h, double* poses);
 /* The pairs setPairObs received (builds the block structure once). */
 int slam_graph_set_edges(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges);
+/* Odometry edges (no reference counterpart): pose b ("bfr", the
+ * earlier one) tied to pose a ("aft") by a measured relative motion rel = (zx,
+ * zy, ztheta) in the axes of pose b, with standard deviations sigma.  With c =
+ * cos theta_b, s = sin theta_b, dx = x_a - x_b, dy = y_a - y_b:
+ *   err   = (c dx + s dy - zx, -s dx + c dy - zy, wrap(wrap(theta_a - theta_b) - ztheta))
+ *   Omega = diag(1/sigma_x^2, 1/sigma_y^2, 1/sigma_theta^2)
+ *   J_b   = [[-c, -s, -s dx + c dy], [s, -c, -c dx - s dy], [0, 0, -1]]
+ *   J_a   = [[ c,  s, 0], [-s, c, 0], [0, 0, 1]]
+ * and the edge's 42 values are those of a landmark edge, in the same order.
+ * The record shares its size and its index prefix with slam_graph_edge. */
+typedef struct {
+    int64_t time_bfr, pose_bfr, time_aft, pose_aft;   /* as slam_graph_edge */
+    double rel[3];
+    double sigma[3];
+} slam_graph_odom;                                     /* 80 bytes */
+/* slam_graph_set_edges with n_odom odometry edges behind the landmark pairs:
+ * the handle's edge set is the concatenation, landmark edges first, E =
+ * n_edges + n_odom columns.  slam_graph_get_system's `blocks`, slam_graph_chi2's
+ * per-edge arrays and slam_graph_get_edge_weights are over all E columns in that
+ * order, and slam_graph_chi2's totals are those of the whole set (bit-identical
+ * from call to call; they depend on (n_edges, n_odom) alone).  Odometry edges
+ * are never down-weighted: w = 1 and rho = chi2 under every robust kind (the
+ * weights reject wrong pairings, and an odometry edge has no association to get
+ * wrong).  A pose that no landmark pair touches but an odometry edge does is
+ * among the set's times: it is updated, and slam_graph_marginals covers it.
+ * slam_graph_set_edges(h, n, e) is slam_graph_set_edges_odom(h, n, e, 0, NULL):
+ * with n_odom = 0 the handle launches the kernels and computes the bits it
+ * did before this entry existed.
+ *
+ * SLAM_ERR_ARG, checked on the host before any HIP call (the handle is left as
+ * it was): a NULL handle, a negative count, a NULL array with a positive
+ * count, poses not set, a pose / time index out of range, time_bfr == time_aft
+ * in an odometry edge, a non-finite rel, and a sigma component that is not
+ * finite and > 0. */
+int slam_graph_set_edges_odom(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges,
+                              int64_t n_odom, const slam_graph_odom* odom);
 /* updateEstPose: linearise every edge at the current poses, assemble H and
  * b, gate, solve, update the poses.  stats[4] = {is_calc, sum delta^2, det,
  * cond} (:514).  On the PCG path det is NaN (not formed at this size) and cond
@@ -1003,7 +1039,8 @@ int slam_graph_optimize(slam_graph* h, double delta_sum_th, int32_t max_iter, do
                         int32_t* n_iter);
 /* The last assembled system: times (n_times), H (3n_times squared, dense, or
  * NULL), b (3 n_times or NULL), blocks (n_edges x 42: BB, BA, AB, AA, b_B, b_A
- * or NULL).  n_times may be queried with everything else NULL. */
+ * or NULL).  n_times may be queried with everything else NULL.  n_edges here is
+ * all E columns of the set: the landmark edges, then the odometry edges. */
 int slam_graph_get_system(slam_graph* h, int64_t* n_times, int64_t* times, double* H, double* b,
                           double* blocks);
 /* The block-sparse H of the last update (block rows/columns are time ranks,
@@ -1111,14 +1148,17 @@ int slam_graph_set_robust(slam_graph* h, int32_t kind, double param);
  * slam_graph_get_system, get_delta, timing, cond_info, gate_info and
  * slam_graph_get_edge_weights alone.  With no edges it returns SLAM_OK with the
  * totals zero.  SLAM_ERR_ARG for a NULL handle or NULL totals (checked before
- * the handle is read; the outputs are not written). */
+ * the handle is read; the outputs are not written).  With odometry edges
+ * (slam_graph_set_edges_odom) n_edges is all E columns, landmark edges first,
+ * and the odometry columns carry w = 1, rho = chi2. */
 int slam_graph_chi2(slam_graph* h, double* totals, double* chi2, double* weight);
 /* chi2_e and w_e as the last linearisation stored them (n_edges each, or NULL):
  * the weights the last assembled H actually used, i.e. those at the poses
  * BEFORE the update that linearised.  SLAM_ERR_ARG when nothing has been
  * linearised since slam_graph_set_edges, and when that linearisation ran with
  * kind none: the unweighted kernel stores no rows (every weight was 1), and
- * the poses it ran at are gone after the update -- use slam_graph_chi2. */
+ * the poses it ran at are gone after the update -- use slam_graph_chi2.  Over
+ * all E columns, landmark edges first (odometry columns: w = 1). */
 int slam_graph_get_edge_weights(slam_graph* h, double* chi2, double* weight);
 /* HalfEdge (graph_based_slam.py:259-300) with its Observation (:20-75). */
 typedef struct {

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <string>
 #include <vector>
 
 #include "device_mem.hpp"
@@ -38,6 +39,7 @@ struct slam_graph {
     double* poses = nullptr;
     // edges and structure
     int64_t E = 0, nt = 0, n_slots = 0;
+    int64_t E_lm = 0;              // landmark edges: columns [0, E_lm); odometry edges behind them
     std::vector<int64_t> times_h;
     slam_graph_edge* edges = nullptr;
     double* blocks = nullptr;      // [42][E]
@@ -240,7 +242,9 @@ int finish_structure(slam_graph* h, int64_t E, int64_t nt, int64_t ns) {
 }
 
 // the structure on the device (graph_build.inl)
-int build_structure_device(slam_graph* h, int64_t E, const slam_graph_edge* ed) {
+int build_structure_device(slam_graph* h, const int64_t n_lm, const slam_graph_edge* ed,
+                           const int64_t n_od, const slam_graph_odom* od) {
+    const int64_t E = n_lm + n_od;
     const int64_t nt_ub = std::min<int64_t>(2 * E, h->T);
     const int64_t K = 2 * E + nt_ub;
     const int tbits = bits_for((uint64_t)h->T);
@@ -268,7 +272,14 @@ int build_structure_device(slam_graph* h, int64_t E, const slam_graph_edge* ed) 
     {
         BuildScratch bs{};
         GTRY(carve_edge_set(h, E, nt_ub, tb, &bs));
-        SLAM_HIP_TRY(hipMemcpyAsync(h->edges, ed, E * sizeof(slam_graph_edge), hipMemcpyHostToDevice, s));
+        // the two records share size and index prefix: the odometry edges go behind
+        // the landmark edges of the same device array
+        if (n_lm)
+            SLAM_HIP_TRY(hipMemcpyAsync(h->edges, ed, n_lm * sizeof(slam_graph_edge),
+                                        hipMemcpyHostToDevice, s));
+        if (n_od)
+            SLAM_HIP_TRY(hipMemcpyAsync(h->edges + n_lm, od, n_od * sizeof(slam_graph_odom),
+                                        hipMemcpyHostToDevice, s));
         // distinct times (:457-467 order)
         hipLaunchKernelGGL(gb_times_kernel, dim3(nblk(E)), dim3(256), 0, s, E, h->edges, bs.tl);
         size_t t = bs.tmp_bytes;
@@ -331,7 +342,17 @@ qfail:
 }
 
 // the same arrays from a host pass (SLAM_GRAPH_HOST_BUILD=1; the tests compare the two)
-int build_structure_host(slam_graph* h, int64_t E, const slam_graph_edge* ed) {
+int build_structure_host(slam_graph* h, const int64_t n_lm, const slam_graph_edge* ed_lm,
+                         const int64_t n_od, const slam_graph_odom* od) {
+    const int64_t E = n_lm + n_od;
+    std::vector<slam_graph_edge> all;      // the concatenation (only with odometry edges)
+    const slam_graph_edge* ed = ed_lm;
+    if (n_od) {
+        all.resize((size_t)E);
+        if (n_lm) std::memcpy(all.data(), ed_lm, (size_t)n_lm * sizeof(slam_graph_edge));
+        std::memcpy(all.data() + n_lm, od, (size_t)n_od * sizeof(slam_graph_odom));
+        ed = all.data();
+    }
     std::vector<int64_t> tl;
     tl.reserve(2 * E);
     for (int64_t e = 0; e < E; ++e) {
@@ -408,10 +429,52 @@ int build_structure_host(slam_graph* h, int64_t E, const slam_graph_edge* ed) {
     return SLAM_OK;
 }
 
-int build_structure(slam_graph* h, int64_t E, const slam_graph_edge* ed) {
+int build_structure(slam_graph* h, int64_t n_lm, const slam_graph_edge* ed, int64_t n_od,
+                    const slam_graph_odom* od) {
     const char* hb = std::getenv("SLAM_GRAPH_HOST_BUILD");
-    if (hb && hb[0] == '1') return build_structure_host(h, E, ed);
-    return build_structure_device(h, E, ed);
+    if (hb && hb[0] == '1') return build_structure_host(h, n_lm, ed, n_od, od);
+    return build_structure_device(h, n_lm, ed, n_od, od);
+}
+
+// slam_graph_set_edges / slam_graph_set_edges_odom after their pointer checks:
+// every record is checked on the host before the handle changes; the edge set
+// is the concatenation, landmark edges first.  E_lm is set only once the
+// structure stands; a build that fails leaves the handle with no edge set.
+int set_edge_set(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges, int64_t n_odom,
+                 const slam_graph_odom* odom, const std::string& entry) {
+    for (int64_t e = 0; e < n_edges; ++e) {
+        const slam_graph_edge& d = edges[e];
+        SLAM_ARG_CHECK(d.pose_bfr >= 0 && d.pose_bfr < h->T && d.pose_aft >= 0 && d.pose_aft < h->T &&
+                           d.time_bfr >= 0 && d.time_bfr < h->T && d.time_aft >= 0 &&
+                           d.time_aft < h->T,
+                       entry + ": pose / time index out of range");
+    }
+    for (int64_t e = 0; e < n_odom; ++e) {
+        const slam_graph_odom& d = odom[e];
+        SLAM_ARG_CHECK(d.pose_bfr >= 0 && d.pose_bfr < h->T && d.pose_aft >= 0 && d.pose_aft < h->T &&
+                           d.time_bfr >= 0 && d.time_bfr < h->T && d.time_aft >= 0 &&
+                           d.time_aft < h->T,
+                       entry + ": pose / time index of an odometry edge out of range");
+        SLAM_ARG_CHECK(d.time_bfr != d.time_aft, entry + ": odometry edge with time_bfr == time_aft");
+        for (int k = 0; k < 3; ++k) {
+            SLAM_ARG_CHECK(std::isfinite(d.rel[k]), entry + ": odometry rel is not finite");
+            SLAM_ARG_CHECK(std::isfinite(d.sigma[k]) && d.sigma[k] > 0.0,
+                           entry + ": odometry sigma must be finite and > 0");
+        }
+    }
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    h->assembled = false;
+    h->marg_last_iters = 0;
+    h->lin_kind = -1;
+    int rc = SLAM_OK;
+    if (n_edges + n_odom) rc = build_structure(h, n_edges, edges, n_odom, odom);
+    if (rc || n_edges + n_odom == 0) {
+        h->E = h->E_lm = h->nt = h->n_slots = 0;
+        h->times_h.clear();
+        return rc;
+    }
+    h->E_lm = n_edges;
+    return SLAM_OK;
 }
 
 GraphConst gconst(const slam_graph_config& c) { return GraphConst{c.r_dist, c.r_dir, c.r_orient}; }
@@ -439,17 +502,27 @@ int robust_reserve(slam_graph* h) {
 
 // the linearise launch of both sites (linearize_assemble, slam_graph_marginals)
 // with the handle's robust kind; a none handle takes the unweighted
-// instantiation and never allocates the rows
+// instantiation and never allocates the rows.  A set without odometry edges
+// launches the default instantiation over all E columns and nothing else; with
+// them the landmark columns [0, E_lm) take the MIXED one (E is the stride) and
+// graph_linearize_odom_kernel the tail [E_lm, E).
 int launch_linearize(slam_graph* h) {
     const int32_t kind = h->robust_kind;
+    const int64_t n_od = h->E - h->E_lm;
     double* rows = nullptr;
     if (kind != SLAM_GRAPH_ROBUST_NONE) {
         GTRY(robust_reserve(h));
         rows = robust_rows(h).lin;
     }
-#define SLAM_LINEARIZE(K)                                                                         \
-    hipLaunchKernelGGL(graph_linearize_kernel<K>, dim3(nblk(h->E)), dim3(256), 0, h->stream, h->E, \
-                       h->edges, h->poses, gconst(h->cfg), h->blocks, h->robust_param, rows)
+#define SLAM_LINEARIZE(K)                                                                          \
+    if (n_od == 0)                                                                                 \
+        hipLaunchKernelGGL(graph_linearize_kernel<K>, dim3(nblk(h->E)), dim3(256), 0, h->stream,   \
+                           h->E, h->edges, h->poses, gconst(h->cfg), h->blocks, h->robust_param,   \
+                           rows, (int64_t)0);                                                      \
+    else if (h->E_lm)                                                                              \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(graph_linearize_kernel<K, true>), dim3(nblk(h->E_lm)),  \
+                           dim3(256), 0, h->stream, h->E, h->edges, h->poses, gconst(h->cfg),      \
+                           h->blocks, h->robust_param, rows, h->E_lm)
     switch (kind) {
         case SLAM_GRAPH_ROBUST_HUBER: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_HUBER); break;
         case SLAM_GRAPH_ROBUST_CAUCHY: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_CAUCHY); break;
@@ -457,6 +530,9 @@ int launch_linearize(slam_graph* h) {
         default: SLAM_LINEARIZE(SLAM_GRAPH_ROBUST_NONE); break;      // set_robust admits no other
     }
 #undef SLAM_LINEARIZE
+    if (n_od)
+        hipLaunchKernelGGL(graph_linearize_odom_kernel, dim3(nblk(n_od)), dim3(256), 0, h->stream,
+                           h->E_lm, h->E, h->edges, h->poses, h->blocks, rows);
     h->lin_kind = kind;
     return SLAM_OK;
 }
@@ -466,9 +542,16 @@ int launch_linearize(slam_graph* h) {
 int launch_chi2(slam_graph* h, double* rows) {
     const RobustRows r = robust_rows(h);
     const unsigned nb = nblk(h->E, kChi2Threads);
+    const bool mixed = h->E_lm < h->E;
 #define SLAM_CHI2(K)                                                                               \
-    hipLaunchKernelGGL(graph_chi2_kernel<K>, dim3(nb), dim3(kChi2Threads), 0, h->stream, h->E,     \
-                       h->edges, h->poses, gconst(h->cfg), h->robust_param, rows, r.part)
+    if (!mixed)                                                                                    \
+        hipLaunchKernelGGL(graph_chi2_kernel<K>, dim3(nb), dim3(kChi2Threads), 0, h->stream, h->E, \
+                           h->edges, h->poses, gconst(h->cfg), h->robust_param, rows, r.part,      \
+                           (int64_t)0);                                                            \
+    else                                                                                           \
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(graph_chi2_kernel<K, true>), dim3(nb),                  \
+                           dim3(kChi2Threads), 0, h->stream, h->E, h->edges, h->poses,             \
+                           gconst(h->cfg), h->robust_param, rows, r.part, h->E_lm)
     switch (h->robust_kind) {
         case SLAM_GRAPH_ROBUST_HUBER: SLAM_CHI2(SLAM_GRAPH_ROBUST_HUBER); break;
         case SLAM_GRAPH_ROBUST_CAUCHY: SLAM_CHI2(SLAM_GRAPH_ROBUST_CAUCHY); break;
@@ -1187,23 +1270,17 @@ int slam_graph_get_poses(slam_graph* h, double* poses) {
 int slam_graph_set_edges(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges) {
     SLAM_ARG_CHECK(h && n_edges >= 0 && (edges || n_edges == 0), "slam_graph_set_edges: bad arguments");
     SLAM_ARG_CHECK(h->poses, "slam_graph_set_edges: set the poses first");
-    for (int64_t e = 0; e < n_edges; ++e) {
-        const slam_graph_edge& d = edges[e];
-        SLAM_ARG_CHECK(d.pose_bfr >= 0 && d.pose_bfr < h->T && d.pose_aft >= 0 && d.pose_aft < h->T &&
-                           d.time_bfr >= 0 && d.time_bfr < h->T && d.time_aft >= 0 &&
-                           d.time_aft < h->T,
-                       "slam_graph_set_edges: pose / time index out of range");
-    }
-    SLAM_HIP_TRY(hipSetDevice(h->device));
-    h->assembled = false;
-    h->marg_last_iters = 0;
-    h->lin_kind = -1;
-    if (n_edges == 0) {
-        h->E = h->nt = h->n_slots = 0;
-        h->times_h.clear();
-        return SLAM_OK;
-    }
-    return build_structure(h, n_edges, edges);
+    return set_edge_set(h, n_edges, edges, 0, nullptr, "slam_graph_set_edges");
+}
+
+int slam_graph_set_edges_odom(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges,
+                              int64_t n_odom, const slam_graph_odom* odom) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_edges_odom: NULL handle");
+    SLAM_ARG_CHECK(n_edges >= 0 && n_odom >= 0, "slam_graph_set_edges_odom: negative count");
+    SLAM_ARG_CHECK((edges || n_edges == 0) && (odom || n_odom == 0),
+                   "slam_graph_set_edges_odom: NULL array with a positive count");
+    SLAM_ARG_CHECK(h->poses, "slam_graph_set_edges_odom: set the poses first");
+    return set_edge_set(h, n_edges, edges, n_odom, odom, "slam_graph_set_edges_odom");
 }
 
 int slam_graph_update(slam_graph* h, double* stats) {

@@ -199,16 +199,20 @@ __device__ __forceinline__ void robust_weight(const double chi2, const double pa
 // AA (row-major 3x3), b_B, b_A.  KIND != none: every one of the 42 values is
 // multiplied by the edge's weight, and rows ([2][E]: chi2, w) receives what the
 // weight came from; the none instantiation reads neither param nor rows.
-template <int KIND>
+// MIXED (an edge set with odometry columns behind the landmark ones, DESIGN
+// 8.4): E stays the column stride of blocks and rows, and the lanes stop at
+// n_lm; the default instantiation does not read n_lm.
+template <int KIND, bool MIXED = false>
 __global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
                                                               const slam_graph_edge* __restrict__ edges,
                                                               const double* __restrict__ poses,
                                                               const GraphConst g,
                                                               double* __restrict__ blocks,
                                                               const double param,
-                                                              double* __restrict__ rows) {
+                                                              double* __restrict__ rows,
+                                                              const int64_t n_lm) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+    if (e >= (MIXED ? n_lm : E)) return;
     const slam_graph_edge ed = edges[e];
     const double* xb = poses + 3 * ed.pose_bfr;
     const double* xa = poses + 3 * ed.pose_aft;
@@ -239,6 +243,98 @@ __global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
     };
     mat3_tmul(Jb, W, JbW);
     mat3_tmul(Ja, W, JaW);
+    mat3_mul(JbW, Jb, out);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) put(q, out[q]);
+    mat3_mul(JbW, Ja, out);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) put(9 + q, out[q]);
+    mat3_mul(JaW, Jb, out);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) put(18 + q, out[q]);
+    mat3_mul(JaW, Ja, out);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) put(27 + q, out[q]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double acc = JbW[3 * i] * err[0];
+        acc = fma(JbW[3 * i + 1], err[1], acc);
+        put(36 + i, fma(JbW[3 * i + 2], err[2], acc));
+        acc = JaW[3 * i] * err[0];
+        acc = fma(JaW[3 * i + 1], err[1], acc);
+        put(39 + i, fma(JaW[3 * i + 2], err[2], acc));
+    }
+}
+
+// ------------------------------------------------------- odometry edges
+// DESIGN 8.4 (no reference counterpart).  The record shares its size and its
+// index prefix with slam_graph_edge, so the concatenated device array feeds the
+// structure build unchanged and the tail columns are read through this type.
+static_assert(sizeof(slam_graph_odom) == sizeof(slam_graph_edge) &&
+                  offsetof(slam_graph_odom, time_bfr) == offsetof(slam_graph_edge, time_bfr) &&
+                  offsetof(slam_graph_odom, pose_bfr) == offsetof(slam_graph_edge, pose_bfr) &&
+                  offsetof(slam_graph_odom, time_aft) == offsetof(slam_graph_edge, time_aft) &&
+                  offsetof(slam_graph_odom, pose_aft) == offsetof(slam_graph_edge, pose_aft) &&
+                  offsetof(slam_graph_odom, rel) == offsetof(slam_graph_edge, obs_bfr),
+              "slam_graph_odom must share slam_graph_edge's size and index prefix");
+
+// err and the diagonal of Omega of one odometry edge at the current estimates,
+// with the rotation (c, s) = (cos, sin)(theta_b) and the offset (dx, dy) they
+// were formed from: the one statement of both, shared by the linearise and the
+// chi-square kernels.
+//   err = (c dx + s dy - zx, -s dx + c dy - zy, wrap(wrap(theta_a - theta_b) - ztheta))
+__device__ __forceinline__ void odom_err_info(const slam_graph_odom& od, const double* xb,
+                                              const double* xa, double* err, double* om,
+                                              double* csd) {
+    double s, c;
+    sincos(xb[2], &s, &c);
+    const double dx = xa[0] - xb[0], dy = xa[1] - xb[1];
+    err[0] = fma(s, dy, c * dx) - od.rel[0];
+    err[1] = fma(c, dy, -s * dx) - od.rel[1];
+    err[2] = wrap_angle(wrap_angle(xa[2] - xb[2]) - od.rel[2]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) om[i] = 1.0 / (od.sigma[i] * od.sigma[i]);
+    csd[0] = c;
+    csd[1] = s;
+    csd[2] = dx;
+    csd[3] = dy;
+}
+
+__device__ __forceinline__ double odom_chi2(const double* err, const double* om) {
+    double c = err[0] * (om[0] * err[0]);
+    c = fma(err[1], om[1] * err[1], c);
+    return fma(err[2], om[2] * err[2], c);
+}
+
+// One lane per odometry edge, over the tail columns [n_lm, E) of the same
+// [42][E] blocks (and of rows, when the handle has a robust kind: chi2_e and
+// w_e = 1 -- an odometry edge is never down-weighted).
+__global__ __launch_bounds__(256) void graph_linearize_odom_kernel(
+    const int64_t n_lm, const int64_t E, const slam_graph_edge* __restrict__ edges,
+    const double* __restrict__ poses, double* __restrict__ blocks, double* __restrict__ rows) {
+    const int64_t e = n_lm + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const slam_graph_odom od = reinterpret_cast<const slam_graph_odom*>(edges)[e];
+    double err[3], om[3], csd[4];
+    odom_err_info(od, poses + 3 * od.pose_bfr, poses + 3 * od.pose_aft, err, om, csd);
+    if (rows) {
+        rows[e] = odom_chi2(err, om);
+        rows[E + e] = 1.0;
+    }
+    const double c = csd[0], s = csd[1], dx = csd[2], dy = csd[3];
+    const double g0 = fma(c, dy, -s * dx), g1 = -fma(s, dy, c * dx);
+    const double Jb[9] = {-c, -s, g0, s, -c, g1, 0.0, 0.0, -1.0};
+    const double Ja[9] = {c, s, 0.0, -s, c, 0.0, 0.0, 0.0, 1.0};
+    // J^T Omega, Omega diagonal: column j of J^T scaled by om[j]
+    double JbW[9], JaW[9], out[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            JbW[3 * i + j] = Jb[3 * j + i] * om[j];
+            JaW[3 * i + j] = Ja[3 * j + i] * om[j];
+        }
+    auto put = [&](const int row, const double v) { blocks[(int64_t)row * E + e] = v; };
     mat3_mul(JbW, Jb, out);
 #pragma unroll
     for (int q = 0; q < 9; ++q) put(q, out[q]);
@@ -1702,16 +1798,33 @@ constexpr int kChi2Threads = 128;
 constexpr int kChi2FoldThreads = 256;
 constexpr double kChi2LowWeight = 0.1;
 
-template <int KIND>
+//
+// MIXED: the columns [n_lm, E) are odometry edges -- chi2 from
+// odom_err_info, w = 1 and rho = chi2 whatever KIND -- so the boundary
+// workgroup holds both kinds of edge; the workgroups, the partials and the fold
+// are the same, and the totals depend on (n_lm, E - n_lm) alone.  The default
+// instantiation does not read n_lm.
+template <int KIND, bool MIXED = false>
 __global__ __launch_bounds__(kChi2Threads) void graph_chi2_kernel(
     const int64_t E, const slam_graph_edge* __restrict__ edges, const double* __restrict__ poses,
-    const GraphConst g, const double param, double* __restrict__ rows, double* __restrict__ part) {
+    const GraphConst g, const double param, double* __restrict__ rows, double* __restrict__ part,
+    const int64_t n_lm) {
     __shared__ double sh[3 * kChi2Threads / 64];
     const int64_t nb = gridDim.x;
     const int64_t e = (int64_t)blockIdx.x * kChi2Threads + threadIdx.x;
     double v[3] = {0.0, 0.0, 0.0};      // chi2, rho, low-weight count
     double mx = -__builtin_huge_val();
-    if (e < E) {
+    if (MIXED && e >= n_lm && e < E) {
+        const slam_graph_odom od = reinterpret_cast<const slam_graph_odom*>(edges)[e];
+        double err[3], om[3], csd[4];
+        odom_err_info(od, poses + 3 * od.pose_bfr, poses + 3 * od.pose_aft, err, om, csd);
+        const double chi2 = odom_chi2(err, om);
+        rows[e] = chi2;
+        rows[E + e] = 1.0;
+        v[0] = chi2;
+        v[1] = chi2;
+        mx = chi2;
+    } else if (e < E) {
         const slam_graph_edge ed = edges[e];
         double err[3], W[9];
         edge_err_info(ed, poses + 3 * ed.pose_bfr, poses + 3 * ed.pose_aft, g, err, W);

@@ -39,7 +39,7 @@ import numpy as np
 
 from slamhip import _lib
 from slamhip._lib import check, dptr
-from slamhip.graph import DeviceGraph, edge_array, pair_halves
+from slamhip.graph import ODOM_DTYPE, DeviceGraph, edge_array, pair_halves, relpose
 
 BASE_ANG = np.pi / 2.0       # mylib/transform.py:12
 
@@ -217,11 +217,37 @@ class TrajectoryEstimator(object):
         self._times = []
         self._device = device
         self._pairs = None          # the pair list estimate_trajectory last handed to the device
+        self._odom_sigma = None     # setOdometry: None = no odometry edges (the default)
+        self._odom = [None]         # per pose id: the rel of the step that led to it
         self._dev = DeviceGraph(solver=solver, device=device, robust=robust)
 
-    def addPose(self, aPose, aIsObs):
+    def setOdometry(self, sigma):
+        """Odometry edges (no reference counterpart): with ``sigma`` =
+        (sx, sy, stheta) every edge set handed to the device is followed by one
+        odometry edge per step recorded through ``addPose(..., aOdom=rel)``
+        (time = pose id = k-1 -> k); ``None`` switches them off again."""
+        if sigma is not None:
+            sigma = np.asarray(sigma, dtype=np.float64).reshape(3)
+            if not (np.all(np.isfinite(sigma)) and np.all(sigma > 0)):
+                raise ValueError("odometry sigma must be three finite values > 0")
+        self._odom_sigma = sigma
+
+    def addPose(self, aPose, aIsObs, aOdom=None):
+        """``aOdom``: the relative motion (relpose) of the step that led to this
+        pose, kept for the odometry edges."""
         self._poses.append(aPose)
         self._is_obs.append(aIsObs)
+        self._odom.append(None if aOdom is None else np.asarray(aOdom, dtype=np.float64).reshape(3))
+
+    def _odom_records(self):
+        """The odometry edges of the recorded steps, or None with odometry off."""
+        if self._odom_sigma is None:
+            return None
+        steps = [k for k, r in enumerate(self._odom) if r is not None]
+        rec = np.zeros(len(steps), dtype=ODOM_DTYPE)
+        for i, k in enumerate(steps):
+            rec[i] = (k - 1, k - 1, k, k, self._odom[k], self._odom_sigma)
+        return rec
 
     def setPairObs(self, aHalfEdge1, aHalfEdge2):
         """:362-439 (the blocks are formed on the device at updateEstPose)."""
@@ -269,7 +295,8 @@ class TrajectoryEstimator(object):
         if self._pairs is None:
             return None
         chi2, weight = self._dev.edge_weights()
-        return self._pairs, chi2, weight
+        n = len(self._pairs)        # the landmark pairs come first; odometry edges follow
+        return self._pairs, chi2[:n], weight[:n]
 
     def _upload_poses(self):
         self._dev.set_poses(np.array([np.asarray(p, dtype=np.float64).reshape(3) for p in self._poses]))
@@ -284,12 +311,16 @@ class TrajectoryEstimator(object):
     def updateEstPose(self):
         """:452-514.  Returns (is_calc, delta_sum, det, cond)."""
         is_calc, delta_sum, det, cond = False, 0.0, 0.0, 0.0
-        if len(self._times) * 3 > 3:
+        od = self._odom_records()
+        times = set(self._times)
+        if od is not None:
+            times |= set(od["time_bfr"].tolist()) | set(od["time_aft"].tolist())
+        if len(times) * 3 > 3:
             self._upload_poses()
-            self._dev.set_edges(self._rows)
+            self._dev.set_edges(self._rows, odometry=od)
             is_calc, delta_sum, det, cond = self._dev.update()
             if is_calc:
-                self._write_back(sorted(self._times))
+                self._write_back(sorted(times))
             else:
                 print("can Not calculate trajectory!")
             self._rows, self._lm_ids, self._times = [], [], []
@@ -306,11 +337,14 @@ class TrajectoryEstimator(object):
         def times_of(edges):
             return np.unique(np.concatenate([edges["time_bfr"], edges["time_aft"]])).tolist()
 
+        od = self._odom_records()
+        od_times = [] if od is None else times_of(od)
         pending = edge_array(self._rows) if len(self._rows) else None
         first = np.concatenate([pending, paired]) if pending is not None else paired
         seen = set(self._times)
-        for t in times_of(first) if len(first) else []:
+        for t in (times_of(first) if len(first) else []) + od_times:
             if t not in seen:
+                seen.add(t)
                 self._times.append(t)
         if len(self._times) * 3 <= 3:
             # updateEstPose's leng <= 3 branch (:469): nothing solved, and the
@@ -321,19 +355,19 @@ class TrajectoryEstimator(object):
         self._upload_poses()
         # iteration 1 (:697-706): pairs set before this call -- linearised at
         # their setPairObs time, i.e. at these same poses -- plus this pairing
-        self._dev.set_edges(first)
+        self._dev.set_edges(first, odometry=od)
         self._pairs = first
         st = [self._dev.update()]
         self._write_back(sorted(self._times))
         self._rows, self._lm_ids, self._times = [], [], []
         # later iterations: only the re-paired edges, re-linearised each time;
         # an iteration with is_calc = 0 returns delta_sum = 0 and ends the loop
-        if DELTA_SUM_TH <= st[0][1] and max_iter > 1 and len(paired):
+        if DELTA_SUM_TH <= st[0][1] and max_iter > 1 and (len(paired) or len(od_times)):
             if pending is not None:
-                self._dev.set_edges(paired)
+                self._dev.set_edges(paired, odometry=od)
                 self._pairs = paired
             st += list(self._dev.optimize(DELTA_SUM_TH, max_iter - 1))
-            self._write_back(times_of(paired))
+            self._write_back(sorted(set(times_of(paired)) | set(od_times)))
         return np.array(st, dtype=np.float64).reshape(-1, 4)
 
 
@@ -371,7 +405,14 @@ class Robot(object):
         self._poses.append(actual)
         self._time += 1
         seen = self._observe(actual, len(self._poses) - 1, self._time)
-        self._est.addPose(deepcopy(odometry), seen)
+        # the step's relative motion for the odometry edges: host arithmetic, no draw
+        self._est.addPose(deepcopy(odometry), seen, relpose(self._poses[-2], odometry))
+
+    def setOdometry(self, sigma):
+        """Odometry edges between consecutive poses with standard deviations
+        ``sigma`` = (sx, sy, stheta); None (the default) for none
+        (TrajectoryEstimator.setOdometry)."""
+        self._est.setOdometry(sigma)
 
     def _observe(self, pose, pose_id, t):
         """:658-682: scan, keep a half-edge per observed landmark."""

@@ -286,6 +286,7 @@ SIGNATURES = {
     "slam_graph_set_poses": (C.c_int, [_P, C.c_int64, _D]),
     "slam_graph_get_poses": (C.c_int, [_P, _D]),
     "slam_graph_set_edges": (C.c_int, [_P, C.c_int64, _P]),
+    "slam_graph_set_edges_odom": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "slam_graph_update": (C.c_int, [_P, _D]),
     "slam_graph_optimize": (C.c_int, [_P, C.c_double, C.c_int32, _D, _I32]),
     "slam_graph_get_system": (C.c_int, [_P, _I64, _I64, _D, _D, _D]),

@@ -14,6 +14,10 @@ from ._lib import GRAPH_COND, GRAPH_ROBUST, GRAPH_SOLVER, GraphConfig, check, dp
 EDGE_DTYPE = np.dtype([("time_bfr", "<i8"), ("pose_bfr", "<i8"), ("time_aft", "<i8"),
                        ("pose_aft", "<i8"), ("obs_bfr", "<f8", (3,)), ("obs_aft", "<f8", (3,))])
 
+# slam_graph_odom, 80 bytes: the index prefix of slam_graph_edge, then rel and sigma
+ODOM_DTYPE = np.dtype([("time_bfr", "<i8"), ("pose_bfr", "<i8"), ("time_aft", "<i8"),
+                       ("pose_aft", "<i8"), ("rel", "<f8", (3,)), ("sigma", "<f8", (3,))])
+
 
 HALF_DTYPE = np.dtype([("time", "<i8"), ("pose", "<i8"), ("landmark", "<i8"), ("obs", "<f8", (3,))])
 
@@ -47,7 +51,9 @@ def pair_halves(halves, n_landmarks, device=0):
 
 def edge_array(rows):
     """Edge rows [t_bfr, pose_bfr, d, dir, orient, t_aft, pose_aft, d, dir, orient, (lm)]
-    -> slam_graph_edge records."""
+    -> slam_graph_edge records (no rows: an empty record array)."""
+    if len(rows) == 0:
+        return np.zeros(0, dtype=EDGE_DTYPE)
     rows = np.asarray(rows, dtype=np.float64).reshape(len(rows), -1)
     out = np.zeros(len(rows), dtype=EDGE_DTYPE)
     out["time_bfr"] = rows[:, 0].astype(np.int64)
@@ -57,6 +63,30 @@ def edge_array(rows):
     out["pose_aft"] = rows[:, 6].astype(np.int64)
     out["obs_aft"] = rows[:, 7:10]
     return out
+
+
+def odom_array(rows):
+    """Odometry rows [t_bfr, pose_bfr, t_aft, pose_aft, zx, zy, ztheta, sx, sy, stheta]
+    -> slam_graph_odom records."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(len(rows), 10)
+    out = np.zeros(len(rows), dtype=ODOM_DTYPE)
+    for k, name in enumerate(("time_bfr", "pose_bfr", "time_aft", "pose_aft")):
+        out[name] = rows[:, k].astype(np.int64)
+    out["rel"] = rows[:, 4:7]
+    out["sigma"] = rows[:, 7:10]
+    return out
+
+
+def relpose(xb, xa):
+    """Pose ``xa`` in the axes of pose ``xb``: (c dx + s dy, -s dx + c dy,
+    wrap(theta_a - theta_b)) with c, s = cos, sin of theta_b -- the ``rel`` of an
+    odometry edge.  Unchanged under a rigid motion of both poses."""
+    xb = np.asarray(xb, dtype=np.float64).reshape(3)
+    xa = np.asarray(xa, dtype=np.float64).reshape(3)
+    c, s = np.cos(xb[2]), np.sin(xb[2])
+    dx, dy = xa[0] - xb[0], xa[1] - xb[1]
+    return np.array([c * dx + s * dy, -s * dx + c * dy,
+                     np.mod(xa[2] - xb[2] + np.pi, 2 * np.pi) - np.pi])
 
 
 class DeviceGraph:
@@ -81,6 +111,7 @@ class DeviceGraph:
         self._h = h
         self.n_poses = 0
         self.n_edges = 0
+        self.n_odom = 0
         if robust is not None:
             try:
                 self.set_robust(*robust)
@@ -144,12 +175,25 @@ class DeviceGraph:
         check(self._lib.slam_graph_get_poses(self._h, dptr(out)), "slam_graph_get_poses")
         return out
 
-    def set_edges(self, edges):
+    def set_edges(self, edges, odometry=None):
+        """The edge set: landmark pairs, and with ``odometry`` (ODOM_DTYPE records
+        or odom_array rows) the odometry edges behind them
+        (slam_graph_set_edges_odom).  ``n_edges`` is the total, ``n_odom`` the
+        odometry count; per-edge results are over all of them, pairs first."""
         rec = edges if (isinstance(edges, np.ndarray) and edges.dtype == EDGE_DTYPE) else edge_array(edges)
         rec = np.ascontiguousarray(rec)
-        check(self._lib.slam_graph_set_edges(self._h, len(rec), rec.ctypes.data_as(C.c_void_p)),
-              "slam_graph_set_edges")
-        self.n_edges = len(rec)
+        if odometry is None:
+            check(self._lib.slam_graph_set_edges(self._h, len(rec), rec.ctypes.data_as(C.c_void_p)),
+                  "slam_graph_set_edges")
+            self.n_edges, self.n_odom = len(rec), 0
+            return
+        od = odometry if (isinstance(odometry, np.ndarray) and odometry.dtype == ODOM_DTYPE) \
+            else odom_array(odometry)
+        od = np.ascontiguousarray(od)
+        check(self._lib.slam_graph_set_edges_odom(self._h, len(rec), rec.ctypes.data_as(C.c_void_p),
+                                                  len(od), od.ctypes.data_as(C.c_void_p)),
+              "slam_graph_set_edges_odom")
+        self.n_edges, self.n_odom = len(rec) + len(od), len(od)
 
     def update(self):
         """updateEstPose: returns (is_calc, delta_sum, det, cond)."""
@@ -324,3 +368,18 @@ def circle_graph(n_poses, n_landmarks=64, loops_per_pose=3, seed=0, odom_noise=0
     init = truth + np.cumsum(odom_noise * rs.standard_normal(truth.shape), axis=0)
     init[:, 2] = np.mod(init[:, 2] + np.pi, 2 * np.pi) - np.pi
     return init, truth, rec
+
+
+def circle_graph_odometry(truth, sigma, seed):
+    """Odometry edges of a circle_graph trajectory: one per
+    consecutive pose pair (time = pose id = k-1 -> k), rel = relpose(truth[k-1],
+    truth[k]) + sigma * standard normals of RandomState(1000 + seed), three per
+    edge, drawn in order k = 1 .. T-1.  Returns ODOM_DTYPE records."""
+    truth = np.asarray(truth, dtype=np.float64).reshape(-1, 3)
+    sigma = np.asarray(sigma, dtype=np.float64).reshape(3)
+    rs = np.random.RandomState(1000 + seed)
+    rec = np.zeros(max(len(truth) - 1, 0), dtype=ODOM_DTYPE)
+    for k in range(1, len(truth)):
+        rec[k - 1] = (k - 1, k - 1, k, k, relpose(truth[k - 1], truth[k]) + sigma * rs.standard_normal(3),
+                      sigma)
+    return rec
