@@ -1126,25 +1126,10 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     const int64_t gbase = P.gb[P.rank];
     if (tid < kDistWin) s_cand[tid] = ~0ull;
     if (tid == 0) s_mblk = ~0ull;
-    // ---- loads up front: this lane's blocks tid + kFinThreads k and its leaves
+    // ---- loads up front: this lane's blocks fin_blk(tid, k) and its leaves
     double pm[kFinRegBlocks], q[kFinRegBlocks][11];
     bool has[kFinRegBlocks];
-#pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {     // neighbour pairs (finalize_general_kernel)
-        const int64_t b = fin_blk(tid, 2 * kp);
-        has[2 * kp] = b < nb;
-        has[2 * kp + 1] = b + 1 < nb;
-        const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
-        pm[2 * kp] = t.x;
-        pm[2 * kp + 1] = t.y;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
-            q[2 * kp][j] = u.x;
-            q[2 * kp + 1][j] = u.y;
-        }
-    }
+    fin_load_partials<true, 11>(dp, 0, nb, 0, 0, pm, q, has);
     const int part = tid & (kFinLeafLanes - 1);
     double L[4];                                   // fused-block subtree sums
     {
@@ -1154,10 +1139,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
         for (int j = 0; j < 4; ++j) L[j] = Lp[j];
     }
     const int64_t bx0 = tid + (int64_t)kFinThreads * kFinRegBlocks;   // NP > 2^20 only
-    double mlane = -1.0;
-#pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k)
-        if (has[k]) mlane = fmax(mlane, pm[k]);
+    double mlane = fin_lane_max(pm, has);
     for (int64_t b = bx0; b < nb; b += kFinThreads) mlane = fmax(mlane, dp.pmax()[b]);
     // lane sums scaled by the lane's max; T = sum of w_un (unscaled)
     double acc[12];
@@ -1165,14 +1147,8 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     for (int j = 0; j < 12; ++j) acc[j] = 0.0;
     {
         const double rm = mlane > 0.0 ? 1.0 / mlane : 0.0;
-        auto add = [&](const double p, const double* qq) {
-            if (mlane > 0.0) {
-                const double r = p * rm;
-                acc[0] += r * qq[0];
-                acc[1] += (r * r) * qq[1];
-#pragma unroll
-                for (int j = 2; j < 11; ++j) acc[j] += r * qq[j];
-            }
+        auto add = [&](const double p, const double (&qq)[11]) {
+            if (mlane > 0.0) fin_block_add<0>(p * rm, qq, true, acc);
             acc[11] += p * qq[0];
         };
 #pragma unroll
@@ -1190,41 +1166,20 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     // ---- np.sum buffer partials: 4 lanes per 8192-element buffer, pairwise tree
     for (int64_t c0 = 0; c0 < nfull; c0 += kFinBufPerRound) {
         const int64_t c = c0 + tid / kFinLeafLanes;
-        double v = 0.0;
-        if (c < nfull) {
-            if (c0 > 0) {
-                const double* Lp = dp.leaf() + 16 * c + 4 * part;
+        if (c < nfull && c0 > 0) {
+            const double* Lp = dp.leaf() + 16 * c + 4 * part;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) L[j] = Lp[j];
-            }
-            v = (L[0] + L[1]) + (L[2] + L[3]);
+            for (int j = 0; j < 4; ++j) L[j] = Lp[j];
         }
-        static_assert(kFinLeafLanes == 4, "two quad swaps");
-        {
-            const double o = dpp_f64<kDppXor1>(v);
-            v = (part & 1) ? (o + v) : (v + o);              // left operand = lower lane
-        }
-        {
-            const double o = dpp_f64<kDppXor2>(v);
-            v = (part & 2) ? (o + v) : (v + o);
-        }
+        const double v = fin_buffer_value(L, c < nfull);
         if (part == 0 && c < nfull) sh[c] = v;
     }
     __syncthreads();
     PROBE_AT(0);
-    double M = s_wm[0];
-#pragma unroll
-    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wm[w]);
+    const double M = fin_wg_max(s_wm);
     const double thr = M * (1.0 - 0x1p-48);                 // tie window (2^-48 relative)
-    {
-        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
-        acc[0] *= rl;
-        acc[1] *= rl * rl;
-#pragma unroll
-        for (int j = 2; j < 11; ++j) acc[j] *= rl;
-    }
-#pragma unroll
-    for (int j = 0; j < 12; ++j) s_q[j][tid] = acc[j];
+    fin_rescale_store<0, 11>(acc, mlane, M, true, s_q);
+    s_q[11][tid] = acc[11];                                 // T is not scaled
     // first block holding M, and the first kDistWin candidate blocks (index order)
     if (M > 0.0) {
         unsigned long long mb = ~0ull;
@@ -1261,14 +1216,7 @@ __device__ __forceinline__ void dist_record(const int64_t n, const DeferParts& d
     // with the lower lane on the left (a fixed order; twelve butterflies per
     // wave were a 3.7 us dependent chain of lane permutes)
     for (int j = wave; j < 12; j += kFinWaves) {
-        double r = s_q[j][lane];
-#pragma unroll
-        for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[j][lane + 64 * m];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = xor_f64(r, d);
-            r = (lane & d) ? (o + r) : (r + o);
-        }
+        const double r = fin_row_sum_tree(s_q[j]);
         if (lane == 0) {
             if (j < 11) rec.q[j] = r;
             else rec.T = r;

@@ -1,8 +1,25 @@
 // pf_finalize.inl -- end of a deferred-normalisation PF step (included by
-// pf_kernels.inl).  One workgroup of 512 lanes (8 waves, two per SIMD: the
+// pf_kernels.inl).  Workgroups of 512 lanes (8 waves, two per SIMD: the
 // serial parts of the step end -- np.sum's left-to-right buffer chain, the
 // result record -- run on a wave that shares its SIMD with one other wave
 // only).
+//
+// What is here, in order:
+//   * the formulas of the step end, each one function (the table of DESIGN
+//     5.1): (1) fin_load_partials, (2) fin_lane_max / fin_block_add /
+//     fin_lane_sums, (3) fin_wg_max / fin_rescale_store, (4) fin_buffer_value,
+//     (5) fin_row_sum_tree and fin_row_sum_rows (two orders), (6)
+//     fin_fold_slices, (7) fin_argmax_resolve, (8) fin_degenerate_pass, (9)
+//     fin_export_records, (10) fin_pair_prefix, (11) fin_stage_candidate;
+//     besides fin_load_record, lds_chain_sum and the lane layout fin_blk;
+//   * finalize_slices_kernel: NP > 2^20, one workgroup per slice of 2048
+//     fused blocks beyond the first (1-5, 10);
+//   * fin_next_prefix: the next step's block prefix (10, or a loop);
+//   * finalize_general_kernel: the step end for NP > 2^24 (1-9, 11);
+//   * fin_moment_group: a moment workgroup of a split step end (1-3, 5);
+//   * finalize_fast_kernel<SLICED>: the step end up to 2^24 particles, its
+//     loads in an order of its own (1-11; 6 and 10 when SLICED).
+// dist_record (pf_dist.inl), the sharded filter's record, calls 1-5 too.
 //
 // Work: np.sum of the unnormalised weights from the fused blocks' leaf sums
 // (particle_filter.py:234), the block partials rescaled to the global max and
@@ -101,6 +118,333 @@ __device__ __forceinline__ int64_t fin_blk(const int t, const int k) {
     return 2 * (int64_t)t + (k & 1) + 2 * (int64_t)kFinThreads * (k >> 1);
 }
 
+// ---------------------------------------------------------------------------
+// The formulas of the step end, each written once (DESIGN 5.1 has the table
+// of callers).  Columns of a lane's q[k][] and acc[] hold quantities JQ,
+// JQ + 1, ... of the fused kernel's partial sums ps(): 0 = sum u, 1 = sum
+// u^2 (scaled by the SQUARE of a ratio of maxima), 2.. = the covariance
+// moments.
+
+// (1) The lane's block partials: has[k] and, with PMAX, pm[k] of the blocks
+// b_base + fin_blk(tid, k); then q[k][jq + j] = ps(j0 + j) of them, j < NJ.
+// Neighbour pairs, one 16-byte load per array (the partial arrays hold nb + 1
+// entries).  Called again for a further range it re-forms has[] to the same
+// values.
+template <bool PMAX, int NJ, int NQ>
+__device__ __forceinline__ void fin_load_partials(const DeferParts& dp, const int64_t b_base,
+                                                  const int64_t nb, const int j0, const int jq,
+                                                  double (&pm)[kFinRegBlocks],
+                                                  double (&q)[kFinRegBlocks][NQ],
+                                                  bool (&has)[kFinRegBlocks]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
+        const int64_t b = b_base + fin_blk(tid, 2 * kp);
+        has[2 * kp] = b < nb;
+        has[2 * kp + 1] = b + 1 < nb;
+        const int64_t bb = has[2 * kp] ? b : 0;
+        if constexpr (PMAX) {
+            const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
+            pm[2 * kp] = t.x;
+            pm[2 * kp + 1] = t.y;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j0 + j) + bb);
+            q[2 * kp][jq + j] = u.x;
+            q[2 * kp + 1][jq + j] = u.y;
+        }
+    }
+}
+
+// (2a) the largest block max of the lane's register blocks (-1: none)
+__device__ __forceinline__ double fin_lane_max(const double (&pm)[kFinRegBlocks],
+                                               const bool (&has)[kFinRegBlocks]) {
+    double mlane = -1.0;
+#pragma unroll
+    for (int k = 0; k < kFinRegBlocks; ++k)
+        if (has[k]) mlane = fmax(mlane, pm[k]);
+    return mlane;
+}
+
+// (2b) one block into the lane's sums: r = M_b / mlane; the moments
+// (quantities >= 2) only when `full`
+template <int JQ, int NQ, int NA>
+__device__ __forceinline__ void fin_block_add(const double r, const double (&qq)[NQ], const bool full,
+                                              double (&acc)[NA]) {
+    static_assert(NQ <= NA, "a sum per quantity");
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) {
+        if (JQ + c == 0) acc[c] += r * qq[c];
+        else if (JQ + c == 1) acc[c] += (r * r) * qq[c];
+        else if (full) acc[c] += r * qq[c];
+    }
+}
+
+// (2c) the lane's sums over its register blocks, scaled to the lane's max
+template <int JQ, int NQ>
+__device__ __forceinline__ void fin_lane_sums(const double (&pm)[kFinRegBlocks],
+                                              const double (&q)[kFinRegBlocks][NQ],
+                                              const bool (&has)[kFinRegBlocks], const double mlane,
+                                              const bool full, double (&acc)[NQ]) {
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
+    if (mlane > 0.0) {
+        const double rm = 1.0 / mlane;
+#pragma unroll
+        for (int k = 0; k < kFinRegBlocks; ++k)
+            if (has[k]) fin_block_add<JQ>(pm[k] * rm, q[k], full, acc);
+    }
+}
+
+// (3a) the workgroup's max from the waves' maxima
+__device__ __forceinline__ double fin_wg_max(const double* s_wmax) {
+    double M = s_wmax[0];
+#pragma unroll
+    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
+    return M;
+}
+
+// (3b) the lane's first NQ sums rescaled from the lane's max to M, into row c
+// of s_q (the moments only when `full`)
+template <int JQ, int NQ, int NA>
+__device__ __forceinline__ void fin_rescale_store(const double (&acc)[NA], const double mlane,
+                                                  const double M, const bool full,
+                                                  double (*s_q)[kFinThreads]) {
+    static_assert(NQ <= NA, "a sum per quantity");
+    const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
+#pragma unroll
+    for (int c = 0; c < NQ; ++c) {
+        if (JQ + c == 0) s_q[c][threadIdx.x] = acc[c] * rl;
+        else if (JQ + c == 1) s_q[c][threadIdx.x] = acc[c] * (rl * rl);
+        else if (full) s_q[c][threadIdx.x] = acc[c] * rl;
+    }
+}
+
+// (4) np.sum's value of an 8192-element buffer from its four lanes' leaf
+// subtrees L (0 where the lane has none): (L0 + L1) + (L2 + L3), then the two
+// quad swaps with the lower lane on the left; every lane of the quad gets it
+__device__ __forceinline__ double fin_buffer_value(const double (&L)[4], const bool valid) {
+    static_assert(kFinLeafLanes == 4, "two quad swaps");
+    const int part = threadIdx.x & (kFinLeafLanes - 1);
+    double v = valid ? (L[0] + L[1]) + (L[2] + L[3]) : 0.0;
+    {
+        const double o = dpp_f64<kDppXor1>(v);
+        v = (part & 1) ? (o + v) : (v + o);
+    }
+    {
+        const double o = dpp_f64<kDppXor2>(v);
+        v = (part & 2) ? (o + v) : (v + o);
+    }
+    return v;
+}
+
+// (5) The transposed reduction of a row of s_q: 8 lane-strided adds, then the
+// wave.  Two orders, each kernel keeps its own: `tree` is the xor
+// butterfly with the lower lane on the left, whose four 16-lane rows combine
+// as (r0 + r1) + (r2 + r3); `rows` is wave_sum_rows, ((r0 + r1) + r2) + r3.
+__device__ __forceinline__ double fin_row_strided(const double* row) {
+    const int lane = threadIdx.x & 63;
+    double r = row[lane];
+#pragma unroll
+    for (int m = 1; m < kFinThreads / 64; ++m) r = r + row[lane + 64 * m];
+    return r;
+}
+__device__ __forceinline__ double fin_row_sum_tree(const double* row) {
+    const int lane = threadIdx.x & 63;
+    double r = fin_row_strided(row);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = xor_f64(r, d);
+        r = (lane & d) ? (o + r) : (r + o);
+    }
+    return r;
+}
+__device__ __forceinline__ double fin_row_sum_rows(const double* row) {
+    return wave_sum_rows(fin_row_strided(row));
+}
+
+// (6) quantity j's total r plus the later slices' sums q[g][11], each scaled
+// to its slice max m[g] and rescaled to M, in slice order (global memory or LDS)
+__device__ __forceinline__ double fin_fold_slices(double r, const int j, const int nsl, const double M,
+                                                  const double* m, const double* q) {
+    for (int g = 1; g < nsl; ++g) {
+        const double mg = m[g];
+        if (mg > 0.0) {
+            const double f = mg / M;
+            r = r + q[(int64_t)g * 11 + j] * (j == 1 ? f * f : f);
+        }
+    }
+    return r;
+}
+
+// the LDS words of the argmax (the kernels declare them; a wave still at the
+// tie decision's s_flag must find it unchanged: the step's later flags, such
+// as resample_next, live in words of their own)
+struct FinArgmaxLds {
+    unsigned long long* s_min;
+    int32_t* s_flag;
+    int64_t* s_mi;
+    double* s_xe;           // [3]
+    int* s_ncand;
+    int64_t* s_cblk;        // [kFinCand]
+    FinRecord* s_crec;      // [kFinCand]
+};
+
+// (11) stage block b as an argmax candidate: a slot, then its record (*rec,
+// or loaded once the slot is won)
+__device__ __forceinline__ void fin_stage_candidate(const FinArgmaxLds& a, const DeferParts& dp,
+                                                    const int64_t b, const FinRecord* rec) {
+    const int slot = atomicAdd(a.s_ncand, 1);
+    if (slot < kFinCand) {
+        FinRecord f;
+        if (rec) f = *rec;
+        else fin_load_record(dp, b, f);
+        a.s_cblk[slot] = b;
+        a.s_crec[slot] = f;
+    }
+}
+
+// (7) From the lanes' first blocks cb whose max rounds to mval = fl(M / s)
+// (~0: none) to the answer in s_mi / s_xe (whole workgroup): block bc's
+// record, staged or loaded; unless a smaller weight ahead of the block max
+// rounds to the same maximum (fl(pre / s) == mval), when the block's elements
+// are checked one by one.
+__device__ __forceinline__ void fin_argmax_resolve(const FinArgmaxLds& a, const unsigned long long cb,
+                                                   const int64_t n, const double s, const double mval,
+                                                   const double np_recip, const DeferParts& dp,
+                                                   const double* __restrict__ w_un,
+                                                   const double* __restrict__ xs,
+                                                   const double* __restrict__ ys,
+                                                   const double* __restrict__ ts) {
+    const int tid = threadIdx.x;
+    if (cb != ~0ull) atomicMin(a.s_min, cb);
+    __syncthreads();
+    const int64_t bc = (int64_t)*a.s_min;
+    if (tid == 0) {
+        // block bc's record: staged, or loaded if bc was not a staged candidate
+        int slot = -1;
+        const int nc = min(*a.s_ncand, kFinCand);
+        for (int j = 0; j < nc; ++j)
+            if (a.s_cblk[j] == bc) slot = j;
+        FinRecord f;
+        if (slot >= 0) {
+            f = a.s_crec[slot];
+            // (keeps the LDS reads LDS reads: behind pointers the two branches'
+            // loads otherwise merge into flat loads of a selected address)
+            __asm__ volatile("" ::: "memory");
+        } else {
+            fin_load_record(dp, bc, f);
+        }
+        *a.s_mi = f.pi;
+        a.s_xe[0] = f.xe[0];
+        a.s_xe[1] = f.xe[1];
+        a.s_xe[2] = f.xe[2];
+        *a.s_flag = (f.pre / s == mval) ? 1 : 0;
+        if (*a.s_flag) *a.s_min = ~0ull;
+    }
+    __syncthreads();
+    if (*a.s_flag) {
+        // the first index of the block whose w equals mval
+        for (int e = tid; e < kPartPer; e += kFinThreads) {
+            const int64_t i = bc * kPartPer + e;
+            if (i < n && norm_w(w_un[i], s, np_recip) == mval)
+                atomicMin(a.s_min, (unsigned long long)i);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int64_t i = (int64_t)*a.s_min;
+            *a.s_mi = i;
+            a.s_xe[0] = xs[i];
+            a.s_xe[1] = ys[i];
+            a.s_xe[2] = ts[i];
+        }
+    }
+}
+
+// (8) The degenerate step (s not positive and finite): every weight through
+// the reference's division (norm_w) into a BlockPartial, the workgroup's
+// reduction of them, and the estimate's pose into s_xe.  Slow.
+__device__ __forceinline__ BlockPartial fin_degenerate_pass(
+    const int64_t n, const double* __restrict__ w_un, const double s, const double np_recip,
+    const double* __restrict__ xs, const double* __restrict__ ys, const double* __restrict__ ts,
+    const double* __restrict__ refp, BlockPartial* shp, double* s_xe) {
+    const int tid = threadIdx.x;
+    BlockPartial a;
+    bp_zero(a);
+    const double r0 = refp[0], r1 = refp[1], r2 = refp[2];
+    for (int64_t i = tid; i < n; i += kFinThreads) {
+        const double v = norm_w(w_un[i], s, np_recip);
+        BlockPartial o;
+        o.maxv = v;
+        o.maxi = i;
+        o.sw = v;
+        o.sw2 = v * v;
+        const double d0 = xs[i] - r0, d1 = ys[i] - r1, d2 = ts[i] - r2;
+        const double v0 = v * d0, v1 = v * d1, v2 = v * d2;
+        o.m1[0] = v0; o.m1[1] = v1; o.m1[2] = v2;
+        o.m2[0] = v0 * d0; o.m2[1] = v0 * d1; o.m2[2] = v0 * d2;
+        o.m2[3] = v1 * d1; o.m2[4] = v1 * d2; o.m2[5] = v2 * d2;
+        bp_merge(a, o);
+    }
+    const BlockPartial tot = bp_block_reduce(a, shp);
+    if (tid == 0) {
+        s_xe[0] = xs[tot.maxi];
+        s_xe[1] = ys[tot.maxi];
+        s_xe[2] = ts[tot.maxi];
+    }
+    return tot;
+}
+
+// (9) the batch's earlier records (stored by earlier launches) to the host
+// buffer, by lanes 1..63; this step's record went there from write_result_*
+__device__ __forceinline__ void fin_export_records(const StepIO& io, const bool exp,
+                                                   const int32_t b_first, const int32_t st_now) {
+    const int tid = threadIdx.x;
+    if (exp && tid >= 1 && tid < 64) {
+        for (int32_t k = b_first + tid - 1; k < st_now; k += 63) io.res_host[k] = io.res[k];
+    }
+}
+
+// (10) The two-half exclusive prefix over the lanes of the fused-block totals
+// (whole workgroup, one barrier): lane t holds blocks 2t, 2t + 1 of each half
+// of 2 kFinThreads blocks.  u0[hf] = (M_b / den) * q0 of the half's first
+// block (den = 1: w_un units, x / 1 is x; den = s: the quotient is rounded
+// before the product), the pair sums scanned by wave_excl_scan_rows, the wave
+// totals through scr (2 kFinWaves doubles of LDS), the second half offset by
+// the first half's total tot[0].  pex[hf]: the prefix of block fin_blk(tid,
+// 2 hf); its neighbour's is pex[hf] + u0[hf].  An approximate prefix: the exact
+// cumsum classifies against it with a margin, any fixed order serves.
+__device__ __forceinline__ void fin_pair_prefix(const double (&pm)[kFinRegBlocks],
+                                                const double (&q0)[kFinRegBlocks],
+                                                const bool (&has)[kFinRegBlocks], const double den,
+                                                double* scr, double (&pex)[2], double (&u0)[2],
+                                                double (&tot)[2]) {
+    static_assert(kFinRegBlocks == 4, "two halves of lane pairs");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        u0[hf] = has[2 * hf] ? (pm[2 * hf] / den) * q0[2 * hf] : 0.0;
+        const double u1 = has[2 * hf + 1] ? (pm[2 * hf + 1] / den) * q0[2 * hf + 1] : 0.0;
+        double wt;
+        pex[hf] = wave_excl_scan_rows(u0[hf] + u1, wt);
+        if (lane == 63) scr[hf * kFinWaves + wave] = wt;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        double base = 0.0, all = 0.0;
+#pragma unroll
+        for (int w = 0; w < kFinWaves; ++w) {
+            if (w < wave) base = base + scr[hf * kFinWaves + w];
+            all = all + scr[hf * kFinWaves + w];
+        }
+        pex[hf] = base + pex[hf];
+        tot[hf] = all;
+    }
+    pex[1] = tot[0] + pex[1];
+}
+
 // NP > 2^20 (round 5): slices of 2048 fused blocks beyond the first, one
 // workgroup each, laid out like the finalize's register blocks: the slice's
 // max M_g, its 11 partial sums scaled to M_g (lane sums over the lane's four
@@ -143,76 +487,28 @@ __global__ __launch_bounds__(kFinThreads) void finalize_slices_kernel(const int6
     const int64_t b_base = (int64_t)g * kFinThreads * kFinRegBlocks;
     double pm[kFinRegBlocks], q[kFinRegBlocks][11];
     bool has[kFinRegBlocks];
-#pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-        const int64_t b = b_base + fin_blk(tid, 2 * kp);
-        has[2 * kp] = b < nb;
-        has[2 * kp + 1] = b + 1 < nb;
-        const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
-        pm[2 * kp] = t.x;
-        pm[2 * kp + 1] = t.y;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
-            q[2 * kp][j] = u.x;
-            q[2 * kp + 1][j] = u.y;
-        }
-    }
+    fin_load_partials<true, 11>(dp, b_base, nb, 0, 0, pm, q, has);
     // the slice's buffers: 4 lanes per buffer, pairwise
     {
         const int part = tid & (kFinLeafLanes - 1);
         const int64_t c = (int64_t)g * kFinBufPerRound + tid / kFinLeafLanes;
-        double v = 0.0;
+        double L[4] = {};
         if (c < nfull) {
             const double* Lp = dp.leaf() + 16 * c + 4 * part;
-            v = (Lp[0] + Lp[1]) + (Lp[2] + Lp[3]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) L[j] = Lp[j];
         }
-        {
-            const double o = dpp_f64<kDppXor1>(v);
-            v = (part & 1) ? (o + v) : (v + o);
-        }
-        {
-            const double o = dpp_f64<kDppXor2>(v);
-            v = (part & 2) ? (o + v) : (v + o);
-        }
+        const double v = fin_buffer_value(L, c < nfull);
         if (part == 0 && c < nfull) sl.buf[c] = v;
     }
-    double mlane = -1.0;
-#pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k)
-        if (has[k]) mlane = fmax(mlane, pm[k]);
+    const double mlane = fin_lane_max(pm, has);
     double acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = 0.0;
-    if (mlane > 0.0) {
-        const double rm = 1.0 / mlane;
-#pragma unroll
-        for (int k = 0; k < kFinRegBlocks; ++k) {
-            if (has[k]) {
-                const double r = pm[k] * rm;
-                acc[0] += r * q[k][0];
-                acc[1] += (r * r) * q[k][1];
-#pragma unroll
-                for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
-            }
-        }
-    }
+    fin_lane_sums<0>(pm, q, has, mlane, true, acc);
     const double mx = wave_max_f64(mlane);
     if (lane == 0) s_wmax[wave] = mx;
     __syncthreads();
-    double M = s_wmax[0];
-#pragma unroll
-    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
-    {
-        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
-        acc[0] *= rl;
-        acc[1] *= rl * rl;
-#pragma unroll
-        for (int j = 2; j < 11; ++j) acc[j] *= rl;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) s_q[j][tid] = acc[j];
-    }
+    const double M = fin_wg_max(s_wmax);
+    fin_rescale_store<0, 11>(acc, mlane, M, true, s_q);
     // the slice's argmax candidates (a global candidate in this slice is one:
     // the global max is >= M); the finalize checks them instead of the slice
 #pragma unroll
@@ -228,30 +524,11 @@ __global__ __launch_bounds__(kFinThreads) void finalize_slices_kernel(const int6
     // the next step's block prefix (S1) inside the slice in w_un units (M_b
     // times the block's sum of w_un / M_b): the finalize scales it by 1 / s
     // and offsets it by the slices before, when the next step resamples
-    double u0[2], u1[2], pex[2];
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-        u0[hf] = has[2 * hf] ? pm[2 * hf] * q[2 * hf][0] : 0.0;
-        u1[hf] = has[2 * hf + 1] ? pm[2 * hf + 1] * q[2 * hf + 1][0] : 0.0;
-        double wt;
-        pex[hf] = wave_excl_scan_rows(u0[hf] + u1[hf], wt);
-        if (lane == 63) s_pw[hf][wave] = wt;
-    }
-    __syncthreads();
     {
-        double tot[2];
+        double q0[kFinRegBlocks], u0[2], pex[2], tot[2];
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            double base = 0.0, all = 0.0;
-#pragma unroll
-            for (int w = 0; w < kFinWaves; ++w) {
-                if (w < wave) base = base + s_pw[hf][w];
-                all = all + s_pw[hf][w];
-            }
-            pex[hf] = base + pex[hf];
-            tot[hf] = all;
-        }
-        pex[1] = tot[0] + pex[1];
+        for (int k = 0; k < kFinRegBlocks; ++k) q0[k] = q[k][0];
+        fin_pair_prefix(pm, q0, has, 1.0, &s_pw[0][0], pex, u0, tot);
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
             const int64_t b = b_base + fin_blk(tid, 2 * hf);
@@ -261,14 +538,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_slices_kernel(const int6
         if (tid == 0) sl.u[g] = tot[0] + tot[1];
     }
     for (int j = wave; j < 11; j += kFinWaves) {
-        double r = s_q[j][lane];
-#pragma unroll
-        for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[j][lane + 64 * m];
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = xor_f64(r, d);
-            r = (lane & d) ? (o + r) : (r + o);
-        }
+        const double r = fin_row_sum_tree(s_q[j]);
         if (lane == 0) sl.q[(int64_t)g * 11 + j] = r;
     }
     if (tid < kSliceCand) {
@@ -292,41 +562,12 @@ __device__ void fin_next_prefix(const int64_t n, const int64_t nb, const bool ok
                                 const double (&q0)[kFinRegBlocks], const bool (&has)[kFinRegBlocks],
                                 const double* __restrict__ w_un, const DeferParts& dp,
                                 double* __restrict__ boff, double* sh, double* scr) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (ok && nb <= (int64_t)kFinThreads * kFinRegBlocks) {
         // fused-block totals of w for the next step's exact cumsum (S1) from the
-        // registers (round 6): lane t holds blocks 2t, 2t + 1 of each half of
-        // 2 kFinThreads blocks; both halves' pair sums scanned over the lanes at
-        // once (wave scans, one barrier).  An approximate prefix: the exact
-        // cumsum classifies against it with a margin, any fixed
-        // order serves.
-        static_assert(kFinRegBlocks == 4, "two halves of lane pairs");
-        double t0[2], t1[2], p[2], tot[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            t0[hf] = has[2 * hf] ? (pm[2 * hf] / s) * q0[2 * hf] : 0.0;
-            t1[hf] = has[2 * hf + 1] ? (pm[2 * hf + 1] / s) * q0[2 * hf + 1] : 0.0;
-            p[hf] = t0[hf] + t1[hf];
-        }
-        double wt[2], ex[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            ex[hf] = wave_excl_scan_rows(p[hf], wt[hf]);
-            if (lane == 63) scr[hf * kFinWaves + wave] = wt[hf];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            double base = 0.0, all = 0.0;
-#pragma unroll
-            for (int w = 0; w < kFinWaves; ++w) {
-                if (w < wave) base = base + scr[hf * kFinWaves + w];
-                all = all + scr[hf * kFinWaves + w];
-            }
-            ex[hf] = base + ex[hf];
-            tot[hf] = all;
-        }
-        ex[1] = tot[0] + ex[1];
+        // registers (round 6), each block's M_b / s rounded before the product
+        double ex[2], t0[2], tot[2];
+        fin_pair_prefix(pm, q0, has, s, scr, ex, t0, tot);
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
             const int64_t b = fin_blk(tid, 2 * hf);
@@ -435,27 +676,11 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
         s_min = ~0ull;
         s_flag = 0;
     }
-    // ---- loads, issued up front: this lane's blocks fin_blk(tid, k) (pairs of
-    // neighbours, one 16-byte load per array: the partial arrays hold nb + 1
-    // entries) and its leaves
+    const FinArgmaxLds am{&s_min, &s_flag, &s_mi, s_xe, &s_ncand, s_cblk, s_crec};
+    // ---- loads, issued up front: this lane's blocks fin_blk(tid, k) and its leaves
     double pm[kFinRegBlocks], q[kFinRegBlocks][11];
     bool has[kFinRegBlocks];
-#pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-        const int64_t b = fin_blk(tid, 2 * kp);
-        has[2 * kp] = b < nb;
-        has[2 * kp + 1] = b + 1 < nb;
-        const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
-        pm[2 * kp] = t.x;
-        pm[2 * kp + 1] = t.y;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
-            q[2 * kp][j] = u.x;
-            q[2 * kp + 1][j] = u.y;
-        }
-    }
+    fin_load_partials<true, 11>(dp, 0, nb, 0, 0, pm, q, has);
     const int part = tid & (kFinLeafLanes - 1);
     double L[4];                                   // fused-block subtree sums (buffer tid / 4 < nfull)
     {
@@ -465,26 +690,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     }
     // ---- lane partial sums scaled to the lane's max (rescaled to the global
     // max once that is known); q dies here except the totals q[k][0]
-    double mlane = -1.0;
-#pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k)
-        if (has[k]) mlane = fmax(mlane, pm[k]);
+    const double mlane = fin_lane_max(pm, has);
     double acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = 0.0;
-    if (mlane > 0.0) {
-        const double rm = 1.0 / mlane;
-#pragma unroll
-        for (int k = 0; k < kFinRegBlocks; ++k) {
-            if (has[k]) {
-                const double r = pm[k] * rm;
-                acc[0] += r * q[k][0];
-                acc[1] += (r * r) * q[k][1];
-#pragma unroll
-                for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
-            }
-        }
-    }
+    fin_lane_sums<0>(pm, q, has, mlane, true, acc);
     const double mx = wave_max_f64(mlane);
     if (lane == 0) s_wmax[wave] = mx;
     // ---- np.sum: 8192-element buffers, pairwise inside; slice 0's round of
@@ -492,16 +700,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     // kFinBufPerRound), the later slices' buffer values after
     double s = 0.0;
     {
-        double v = (L[0] + L[1]) + (L[2] + L[3]);
-        static_assert(kFinLeafLanes == 4, "two quad swaps");
-        {
-            const double o = dpp_f64<kDppXor1>(v);
-            v = (part & 1) ? (o + v) : (v + o);          // left operand = lower lane
-        }
-        {
-            const double o = dpp_f64<kDppXor2>(v);
-            v = (part & 2) ? (o + v) : (v + o);
-        }
+        const double v = fin_buffer_value(L, true);
         if (part == 0) sh[tid / kFinLeafLanes] = v;
         __syncthreads();
         if (kFinBufPerRound < nfull && tid == 0) {       // not the last round: fold it now
@@ -518,9 +717,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
         if (c0 + 2048 < nfull && tid == 0) s = lds_chain_sum(s, sh, (int)cnt);
         last_cnt = cnt;
     }
-    double M = s_wmax[0];
-#pragma unroll
-    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
+    double M = fin_wg_max(s_wmax);
     {                                                    // the slices' maxima (every wave alike)
         double msl = -1.0;
         for (int g = 1 + lane; g < sl.nsl; g += 64) msl = fmax(msl, sl.m[g]);
@@ -534,30 +731,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
         s = lds_chain_sum(s, sh, (int)last_cnt);
         __builtin_amdgcn_s_setprio(0);
     }
-    {
-        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
-        acc[0] *= rl;
-        acc[1] *= rl * rl;
-#pragma unroll
-        for (int j = 2; j < 11; ++j) acc[j] *= rl;
-#pragma unroll
-        for (int j = 0; j < 11; ++j) s_q[j][tid] = acc[j];
-    }
+    fin_rescale_store<0, 11>(acc, mlane, M, true, s_q);
     // argmax records of the candidate blocks (fl(M_b / s) == fl(M / s) needs
     // M_b within 2 ulp of M), staged in LDS
 #pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k) {
-        if (has[k] && pm[k] >= M * (1.0 - 0x1p-48)) {
-            const int slot = atomicAdd(&s_ncand, 1);
-            if (slot < kFinCand) {
-                const int64_t b = fin_blk(tid, k);
-                FinRecord f;
-                fin_load_record(dp, b, f);
-                s_cblk[slot] = b;
-                s_crec[slot] = f;
-            }
-        }
-    }
+    for (int k = 0; k < kFinRegBlocks; ++k)
+        if (has[k] && pm[k] >= M * (1.0 - 0x1p-48)) fin_stage_candidate(am, dp, fin_blk(tid, k), nullptr);
     if (nch > nfull) {
         __syncthreads();                                  // sh reused by the tail
         const double tsum = tail_chunk_sum(w_un + nfull * kSumChunk, tail_leaves, tail_ops,
@@ -575,28 +754,11 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
         // ---- the 11 sums: wave w reduces quantities w and w + 8 (lane-strided
         // reads, then a butterfly with the lower lane on the left)
         for (int j = wave; j < 11; j += kFinWaves) {
-            double r = s_q[j][lane];
-#pragma unroll
-            for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[j][lane + 64 * m];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double o = xor_f64(r, d);
-                r = (lane & d) ? (o + r) : (r + o);
-            }
+            const double r = fin_row_sum_tree(s_q[j]);
             if (lane == 0) s_tot[j] = r;
         }
         __syncthreads();                                 // + the slices, rescaled to M, in order
-        if (tid < 11) {
-            double r = s_tot[tid];
-            for (int g = 1; g < sl.nsl; ++g) {
-                const double mg = sl.m[g];
-                if (mg > 0.0) {
-                    const double f = mg / M;
-                    r = r + sl.q[(int64_t)g * 11 + tid] * (tid == 1 ? f * f : f);
-                }
-            }
-            s_tot[tid] = r;
-        }
+        if (tid < 11) s_tot[tid] = fin_fold_slices(s_tot[tid], tid, sl.nsl, M, sl.m, sl.q);
         // ---- argmax: the first block whose max rounds to fl(M / s)
         const double mval = M / s;
         unsigned long long cb = ~0ull;
@@ -621,43 +783,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
                 if (cb == ~0ull && b < nb && v[u] / s == mval) cb = (unsigned long long)b;
             }
         }
-        if (cb != ~0ull) atomicMin(&s_min, cb);
-        __syncthreads();
-        const int64_t bc = (int64_t)s_min;
-        if (tid == 0) {
-            // block bc's record: staged, or loaded if bc was not a staged candidate
-            int slot = -1;
-            const int nc = min(s_ncand, kFinCand);
-            for (int j = 0; j < nc; ++j)
-                if (s_cblk[j] == bc) slot = j;
-            FinRecord f;
-            if (slot >= 0) f = s_crec[slot];
-            else fin_load_record(dp, bc, f);
-            s_mi = f.pi;
-            s_xe[0] = f.xe[0];
-            s_xe[1] = f.xe[1];
-            s_xe[2] = f.xe[2];
-            s_flag = (f.pre / s == mval) ? 1 : 0;
-            if (s_flag) s_min = ~0ull;
-        }
-        __syncthreads();
-        if (s_flag) {
-            // a smaller weight ahead of the block max rounds to the same maximum:
-            // the first index of the block whose w equals mval
-            for (int e = tid; e < kPartPer; e += kFinThreads) {
-                const int64_t i = bc * kPartPer + e;
-                if (i < n && norm_w(w_un[i], s, np_recip) == mval)
-                    atomicMin(&s_min, (unsigned long long)i);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                const int64_t i = (int64_t)s_min;
-                s_mi = i;
-                s_xe[0] = xs[i];
-                s_xe[1] = ys[i];
-                s_xe[2] = ts[i];
-            }
-        }
+        fin_argmax_resolve(am, cb, n, s, mval, np_recip, dp, w_un, xs, ys, ts);
         if (tid == 0) {
             const double f = M / s;                      // back from max-relative to w_un / s
             tot.maxv = mval;
@@ -668,30 +794,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
             for (int j = 0; j < 6; ++j) tot.m2[j] = s_tot[5 + j] * f;
         }
     } else {
-        // ---- every weight through the reference's division (slow, degenerate case)
-        BlockPartial a;
-        bp_zero(a);
-        const double r0 = refp[0], r1 = refp[1], r2 = refp[2];
-        for (int64_t i = tid; i < n; i += kFinThreads) {
-            const double v = norm_w(w_un[i], s, np_recip);
-            BlockPartial o;
-            o.maxv = v;
-            o.maxi = i;
-            o.sw = v;
-            o.sw2 = v * v;
-            const double d0 = xs[i] - r0, d1 = ys[i] - r1, d2 = ts[i] - r2;
-            const double v0 = v * d0, v1 = v * d1, v2 = v * d2;
-            o.m1[0] = v0; o.m1[1] = v1; o.m1[2] = v2;
-            o.m2[0] = v0 * d0; o.m2[1] = v0 * d1; o.m2[2] = v0 * d2;
-            o.m2[3] = v1 * d1; o.m2[4] = v1 * d2; o.m2[5] = v2 * d2;
-            bp_merge(a, o);
-        }
-        tot = bp_block_reduce(a, shp);
-        if (tid == 0) {
-            s_xe[0] = xs[tot.maxi];
-            s_xe[1] = ys[tot.maxi];
-            s_xe[2] = ts[tot.maxi];
-        }
+        tot = fin_degenerate_pass(n, w_un, s, np_recip, xs, ys, ts, refp, shp, s_xe);
     }
     FIN_STAMP(3);
     if (tid == 0) {
@@ -704,11 +807,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_general_kernel(
     }
     __syncthreads();
     FIN_STAMP(4);
-    if (exp && tid >= 1 && tid < 64) {
-        // the batch's earlier records (stored by earlier launches) to the host
-        // buffer; this step's record went there from write_result_xe
-        for (int32_t k = b_first + tid - 1; k < st_now; k += 63) io.res_host[k] = io.res[k];
-    }
+    fin_export_records(io, exp, b_first, st_now);
     if (s_next) {
         double q0[kFinRegBlocks];
 #pragma unroll
@@ -768,59 +867,20 @@ __device__ void fin_moment_group(const int g, const int64_t nb, const DeferParts
     const int32_t st = io.ctr[kCtrMom + fs.par], b_first = io.ctr[2], b_last = io.ctr[3];
     double pm[kFinRegBlocks], q[kFinRegBlocks][kFinMomPer];
     bool has[kFinRegBlocks];
-#pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-        const int64_t b = fin_blk(tid, 2 * kp);
-        has[2 * kp] = b < nb;
-        has[2 * kp + 1] = b + 1 < nb;
-        const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
-        pm[2 * kp] = t.x;
-        pm[2 * kp + 1] = t.y;
-#pragma unroll
-        for (int j = 0; j < kFinMomPer; ++j) {
-            const double2 u = *reinterpret_cast<const double2*>(dp.ps(2 + g * kFinMomPer + j) + bb);
-            q[2 * kp][j] = u.x;
-            q[2 * kp + 1][j] = u.y;
-        }
-    }
+    fin_load_partials<true, kFinMomPer>(dp, 0, nb, 2 + g * kFinMomPer, 0, pm, q, has);
     __asm__ volatile("" ::: "memory");                  // requested before the step is looked at
     if (fin_full_path(fs.full, st, b_first, b_last) || st >= io.cap) return;
-    double mlane = -1.0;
-#pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k)
-        if (has[k]) mlane = fmax(mlane, pm[k]);
+    const double mlane = fin_lane_max(pm, has);
     const double wm = wave_max_f64(mlane);
     if (lane == 0) s_wmax[wave] = wm;
     double acc[kFinMomPer];
-#pragma unroll
-    for (int j = 0; j < kFinMomPer; ++j) acc[j] = 0.0;
-    if (mlane > 0.0) {
-        const double rm = 1.0 / mlane;
-#pragma unroll
-        for (int k = 0; k < kFinRegBlocks; ++k) {
-            if (has[k]) {
-                const double r = pm[k] * rm;
-#pragma unroll
-                for (int j = 0; j < kFinMomPer; ++j) acc[j] += r * q[k][j];
-            }
-        }
-    }
+    fin_lane_sums<2>(pm, q, has, mlane, true, acc);     // (any of the moments: quantity >= 2)
     __syncthreads();                                     // s_wmax
-    double M = s_wmax[0];
-#pragma unroll
-    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
-    {
-        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
-#pragma unroll
-        for (int j = 0; j < kFinMomPer; ++j) s_q[j][tid] = acc[j] * rl;
-    }
+    const double M = fin_wg_max(s_wmax);
+    fin_rescale_store<2, kFinMomPer>(acc, mlane, M, true, s_q);
     __syncthreads();
     if (wave < kFinMomPer) {
-        double r = s_q[wave][lane];
-#pragma unroll
-        for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[wave][lane + 64 * m];
-        r = wave_sum_rows(r);
+        const double r = fin_row_sum_rows(s_q[wave]);
         if (lane == 0) fs.mom[st].tot[2 + g * kFinMomPer + wave] = r;
     }
 #ifdef SLAM_FIN_PROBE
@@ -896,9 +956,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         s_min = ~0ull;
         s_flag = 0;
     }
+    const FinArgmaxLds am{&s_min, &s_flag, &s_mi, s_xe, &s_ncand, s_cblk, s_crec};
     // ---- loads: the leaves, then the partials of the lane's blocks
-    // fin_blk(tid, k) (pairs of neighbours, one 16-byte load per array: the
-    // partial arrays hold nb + 1 entries), the step context, the flag words
+    // fin_blk(tid, k), the step context, the flag words
     // SLICED: the slices' buffer values first (the chain reads them right after
     // the first round's), then the leaves
     const int nsl = SLICED ? sl.nsl : 1;
@@ -922,31 +982,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     }
     double pm[kFinRegBlocks], q[kFinRegBlocks][11];
     bool has[kFinRegBlocks];
-#pragma unroll
-    for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-        const int64_t b = fin_blk(tid, 2 * kp);
-        has[2 * kp] = b < nb;
-        has[2 * kp + 1] = b + 1 < nb;
-        const int64_t bb = has[2 * kp] ? b : 0;
-        const double2 t = *reinterpret_cast<const double2*>(dp.pmax() + bb);
-        pm[2 * kp] = t.x;
-        pm[2 * kp + 1] = t.y;
-    }
+    fin_load_partials<true, 0>(dp, 0, nb, 0, 0, pm, q, has);    // the block maxima
     __asm__ volatile("" ::: "memory");                  // then the partial sums
-    auto load_ps = [&](const int j0, const int j1) {
-#pragma unroll
-        for (int kp = 0; kp < kFinRegBlocks / 2; ++kp) {
-            const int64_t b = fin_blk(tid, 2 * kp);
-            const int64_t bb = b < nb ? b : 0;
-#pragma unroll
-            for (int j = j0; j < j1; ++j) {
-                const double2 u = *reinterpret_cast<const double2*>(dp.ps(j) + bb);
-                q[2 * kp][j] = u.x;
-                q[2 * kp + 1][j] = u.y;
-            }
-        }
-    };
-    load_ps(0, 2);                                      // sum u (the prefix), sum u^2 (the ESS)
+    fin_load_partials<false, 2>(dp, 0, nb, 0, 0, pm, q, has);   // sum u (the prefix), sum u^2 (the ESS)
     // the covariance moments: here on the full path only (a split step end
     // leaves them to the moment workgroups); the path is known once the step
     // counters are in, by when every load above is out
@@ -955,7 +993,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         fin_full_path(fs.full, st_now, b_first, b_last) || st_now >= io.cap)) != 0;
     const int nq = full ? 11 : 2;
     if (full) {
-        load_ps(2, 11);
+        fin_load_partials<false, 9>(dp, 0, nb, 2, 2, pm, q, has);
     } else {
 #pragma unroll
         for (int k = 0; k < kFinRegBlocks; ++k) {
@@ -994,15 +1032,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     // ---- np.sum's buffer values (one round of <= 128 buffers, pairwise inside)
     {
         const int64_t c = tid / kFinLeafLanes;
-        double v = (c < nfull) ? (L[0] + L[1]) + (L[2] + L[3]) : 0.0;
-        {
-            const double o = dpp_f64<kDppXor1>(v);
-            v = (part & 1) ? (o + v) : (v + o);          // left operand = lower lane
-        }
-        {
-            const double o = dpp_f64<kDppXor2>(v);
-            v = (part & 2) ? (o + v) : (v + o);
-        }
+        const double v = fin_buffer_value(L, c < nfull);
         if (part == 0 && c < nfull) sh[c] = v;
     }
     if constexpr (SLICED) {
@@ -1025,10 +1055,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     }
     // ---- block maxima; each wave's argmax candidates (into registers: the
     // lane's first block within 2^-48 of the wave's max)
-    double mlane = -1.0;
-#pragma unroll
-    for (int k = 0; k < kFinRegBlocks; ++k)
-        if (has[k]) mlane = fmax(mlane, pm[k]);
+    const double mlane = fin_lane_max(pm, has);
     const double wm = wave_max_f64(SLICED ? fmax(mlane, slm) : mlane);   // + the slices' maxima
     if (lane == 0) s_wmax[wave] = wm;
     if constexpr (SLICED) {
@@ -1053,55 +1080,17 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     __asm__ volatile("" ::: "memory");                  // requested before the sums wait
     // ---- lane partial sums scaled to the lane's max
     double acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = 0.0;
-    if (mlane > 0.0) {
-        const double rm = 1.0 / mlane;
-#pragma unroll
-        for (int k = 0; k < kFinRegBlocks; ++k) {
-            if (has[k]) {
-                const double r = pm[k] * rm;
-                acc[0] += r * q[k][0];
-                acc[1] += (r * r) * q[k][1];
-                if (full) {
-#pragma unroll
-                    for (int j = 2; j < 11; ++j) acc[j] += r * q[k][j];
-                }
-            }
-        }
-    }
+    fin_lane_sums<0>(pm, q, has, mlane, full, acc);
     __syncthreads();                                     // s_wmax
-    double M = s_wmax[0];
-#pragma unroll
-    for (int w = 1; w < kFinWaves; ++w) M = fmax(M, s_wmax[w]);
-    {
-        const double rl = (mlane > 0.0 && M > 0.0) ? mlane / M : 0.0;
-        acc[0] *= rl;
-        acc[1] *= rl * rl;
-        s_q[0][tid] = acc[0];
-        s_q[1][tid] = acc[1];
-        if (full) {
-#pragma unroll
-            for (int j = 2; j < 11; ++j) s_q[j][tid] = acc[j] * rl;
-        }
-    }
-    if (cblk >= 0 && cpm >= M * (1.0 - 0x1p-48)) {
-        const int slot = atomicAdd(&s_ncand, 1);
-        if (slot < kFinCand) {
-            s_cblk[slot] = cblk;
-            s_crec[slot] = cr;
-        }
-    }
+    const double M = fin_wg_max(s_wmax);
+    fin_rescale_store<0, 11>(acc, mlane, M, full, s_q);
+    if (cblk >= 0 && cpm >= M * (1.0 - 0x1p-48)) fin_stage_candidate(am, dp, cblk, &cr);
     // SLICED: the listed candidates of the slices, records staged the same way
     const bool slc = SLICED && ccb >= 0 && ccp >= M * (1.0 - 0x1p-48);
     if (slc) {
         FinRecord f;
         fin_load_record(dp, ccb, f);
-        const int slot = atomicAdd(&s_ncand, 1);
-        if (slot < kFinCand) {
-            s_cblk[slot] = ccb;
-            s_crec[slot] = f;
-        }
+        fin_stage_candidate(am, dp, ccb, &f);
     }
     if (nch > nfull) {
         __syncthreads();                                 // sh reused by the tail
@@ -1121,25 +1110,12 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
         // reads, then the wave's rows by DPP: a fixed order, no LDS permutes)
         // (a split step end: sum u and sum u^2 only, one round)
         for (int j = wave; j < nq; j += kFinWaves) {
-            double r = s_q[j][lane];
-#pragma unroll
-            for (int m = 1; m < kFinThreads / 64; ++m) r = r + s_q[j][lane + 64 * m];
-            r = wave_sum_rows(r);
+            const double r = fin_row_sum_rows(s_q[j]);
             if (lane == 0) s_tot[j] = r;
         }
         if constexpr (SLICED) {                         // + the slices, rescaled to M, in order
             __syncthreads();
-            if (tid < 11) {
-                double r = s_tot[tid];
-                for (int g = 1; g < nsl; ++g) {
-                    const double mg = s_slm[g];
-                    if (mg > 0.0) {
-                        const double f = mg / M;
-                        r = r + s_slq[g][tid] * (tid == 1 ? f * f : f);
-                    }
-                }
-                s_tot[tid] = r;
-            }
+            if (tid < 11) s_tot[tid] = fin_fold_slices(s_tot[tid], tid, nsl, M, s_slm, &s_slq[0][0]);
         }
         // ---- argmax: the first block whose max rounds to fl(M / s)
         const double mval = M / s;
@@ -1167,43 +1143,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
                 }
             }
         }
-        if (cb != ~0ull) atomicMin(&s_min, cb);
-        __syncthreads();
-        const int64_t bc = (int64_t)s_min;
-        if (tid == 0) {
-            // block bc's record: staged, or loaded if it was not a staged candidate
-            int slot = -1;
-            const int nc = min(s_ncand, kFinCand);
-            for (int j = 0; j < nc; ++j)
-                if (s_cblk[j] == bc) slot = j;
-            FinRecord f;
-            if (slot >= 0) f = s_crec[slot];
-            else fin_load_record(dp, bc, f);
-            s_mi = f.pi;
-            s_xe[0] = f.xe[0];
-            s_xe[1] = f.xe[1];
-            s_xe[2] = f.xe[2];
-            s_flag = (f.pre / s == mval) ? 1 : 0;
-            if (s_flag) s_min = ~0ull;
-        }
-        __syncthreads();
-        if (s_flag) {
-            // a smaller weight ahead of the block max rounds to the same maximum:
-            // the first index of the block whose w equals mval
-            for (int e = tid; e < kPartPer; e += kFinThreads) {
-                const int64_t i = bc * kPartPer + e;
-                if (i < n && norm_w(w_un[i], s, np_recip) == mval)
-                    atomicMin(&s_min, (unsigned long long)i);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                const int64_t i = (int64_t)s_min;
-                s_mi = i;
-                s_xe[0] = xs[i];
-                s_xe[1] = ys[i];
-                s_xe[2] = ts[i];
-            }
-        }
+        fin_argmax_resolve(am, cb, n, s, mval, np_recip, dp, w_un, xs, ys, ts);
         if (tid == 0) {
             const double f = M / s;                      // back from max-relative to w_un / s
             tot.maxv = mval;
@@ -1219,30 +1159,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             }
         }
     } else {
-        // ---- every weight through the reference's division (slow, degenerate case)
-        BlockPartial a;
-        bp_zero(a);
-        const double r0 = refp[0], r1 = refp[1], r2 = refp[2];
-        for (int64_t i = tid; i < n; i += kFinThreads) {
-            const double v = norm_w(w_un[i], s, np_recip);
-            BlockPartial o;
-            o.maxv = v;
-            o.maxi = i;
-            o.sw = v;
-            o.sw2 = v * v;
-            const double d0 = xs[i] - r0, d1 = ys[i] - r1, d2 = ts[i] - r2;
-            const double v0 = v * d0, v1 = v * d1, v2 = v * d2;
-            o.m1[0] = v0; o.m1[1] = v1; o.m1[2] = v2;
-            o.m2[0] = v0 * d0; o.m2[1] = v0 * d1; o.m2[2] = v0 * d2;
-            o.m2[3] = v1 * d1; o.m2[4] = v1 * d2; o.m2[5] = v2 * d2;
-            bp_merge(a, o);
-        }
-        tot = bp_block_reduce(a, shp);
-        if (tid == 0) {
-            s_xe[0] = xs[tot.maxi];
-            s_xe[1] = ys[tot.maxi];
-            s_xe[2] = ts[tot.maxi];
-        }
+        tot = fin_degenerate_pass(n, w_un, s, np_recip, xs, ys, ts, refp, shp, s_xe);
     }
     FIN_STAMP_AT(pb, 3);
     // the batch's last step exports the batch's records (a full step end)
@@ -1266,11 +1183,7 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
     }
     __syncthreads();
     FIN_STAMP_AT(pb, 4);
-    if (exp && tid >= 1 && tid < 64) {
-        // the batch's earlier records (stored by earlier launches) to the host
-        // buffer; this step's record went there from write_result_fw
-        for (int32_t k = b_first + tid - 1; k < st_now; k += 63) io.res_host[k] = io.res[k];
-    }
+    fin_export_records(io, exp, b_first, st_now);
     if constexpr (!SLICED) {
         if (exp && tid >= 64) {
             // and their moment entries (complete by the kernel boundary), as words
@@ -1289,17 +1202,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             // the slices' own prefixes (finalize_slices_kernel), w_un units:
             // slice 0 from the registers the same way, then every block's
             // (U_0 + ... + U_{g-1} + pre_b) / s
-            double u0[2], u1[2], pex[2], tot[2];
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                u0[hf] = has[2 * hf] ? pm[2 * hf] * q0[2 * hf] : 0.0;
-                u1[hf] = has[2 * hf + 1] ? pm[2 * hf + 1] * q0[2 * hf + 1] : 0.0;
-                double wt;
-                pex[hf] = wave_excl_scan_rows(u0[hf] + u1[hf], wt);
-                if (lane == 63) s_q[hf][wave] = wt;
-            }
             // slices g >= 1: block 2048 + tid + 512 i (slice 1 + i / 4, coalesced),
-            // the first batch of 32 requested before the barrier
+            // the first batch of 32 requested before the prefix's barrier
             const int nrest = (nsl - 1) * kFinRegBlocks;
             constexpr int kB = 32;
             auto pre_batch = [&](const int i0, double (&pv)[kB]) {
@@ -1311,19 +1215,8 @@ __global__ __launch_bounds__(kFinThreads) void finalize_fast_kernel(
             };
             double pv[kB];
             pre_batch(0, pv);
-            __syncthreads();
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                double base = 0.0, all = 0.0;
-#pragma unroll
-                for (int w = 0; w < kFinWaves; ++w) {
-                    if (w < wave) base = base + s_q[hf][w];
-                    all = all + s_q[hf][w];
-                }
-                pex[hf] = base + pex[hf];
-                tot[hf] = all;
-            }
-            pex[1] = tot[0] + pex[1];
+            double u0[2], pex[2], tot[2];
+            fin_pair_prefix(pm, q0, has, 1.0, &s_q[0][0], pex, u0, tot);
             const double rs = 1.0 / s;
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {

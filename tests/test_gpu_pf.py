@@ -361,3 +361,37 @@ def test_step_end_against_numpy_on_the_devices_weights(slamhip_pf, n):
     np.testing.assert_allclose(r["ess"], 1.0 / np.dot(w, w), rtol=1e-12)
     np.testing.assert_allclose(r["cov"], po.weighted_cov(x, y, th, w), rtol=1e-8, atol=1e-14)
     assert r["status"] == 0
+
+
+def _step_end_matches_numpy(d, r):
+    w_un, s = d.get_weights_raw()
+    x, y, th, w = d.get_state()
+    print(f"NP {d.n}: weight_sum {r['weight_sum']!r} np.sum {np.sum(w_un)!r} max_val {r['max_val']!r} "
+          f"w.max {w.max()!r} max_idx {r['max_idx']} argmax {int(np.argmax(w))} status {r['status']}")
+    assert r["weight_sum"] == np.sum(w_un)
+    assert r["max_val"] == w.max()
+    assert r["max_idx"] == int(np.argmax(w)) == 0
+    np.testing.assert_array_equal(r["x_est"], [x[r["max_idx"]], y[r["max_idx"]], th[r["max_idx"]]])
+    assert r["status"] == 0
+
+
+@pytest.mark.parametrize("n", [1 << 20, (1 << 21) + 12345, (1 << 24) + 12345])
+def test_step_end_with_every_block_maximum_tied(slamhip_pf, n):
+    """A filter without landmarks keeps its weights uniform, so every fused
+    block's maximum ties and the first argmax is particle 0.  One size per
+    finalize form: at 2^20 the tied candidates overflow the kFinCand staged
+    records (block 0's record is loaded when it was not staged); at 2^21 +
+    12,345 the slice lists more than kSliceCand tied maxima and the fast
+    kernel scans the slice's blocks; at 2^24 + 12,345 the general kernel walks
+    its batched blocks.  Two steps as a batch (a split step end, then a full
+    one, at 2^20) and one stepwise step on a second handle."""
+    lm = np.zeros((0, 2))
+    ctl = np.tile([np.deg2rad(10.0) * 10.0, np.deg2rad(10.0)], (2, 1))
+    with slamhip_pf.DeviceParticleFilter(n, lm, motion="velocity", likelihood="logsum", seed=3) as d:
+        # an empty observation set has no (steps, 0, 2) reshape: the entry point directly
+        slamhip_pf.check(d._lib.slam_pf_load_observations(d._h, 2, None), "slam_pf_load_observations")
+        recs = d.run(0, ctl)
+        assert recs[0]["max_idx"] == 0 and recs[0]["status"] == 0
+        _step_end_matches_numpy(d, recs[1])
+    with slamhip_pf.DeviceParticleFilter(n, lm, motion="velocity", likelihood="logsum", seed=3) as d:
+        _step_end_matches_numpy(d, d.step(ctl[0], np.zeros((0, 2))))
