@@ -1160,6 +1160,56 @@ int slam_graph_chi2(slam_graph* h, double* totals, double* chi2, double* weight)
  * the poses it ran at are gone after the update -- use slam_graph_chi2.  Over
  * all E columns, landmark edges first (odometry columns: w = 1). */
 int slam_graph_get_edge_weights(slam_graph* h, double* chi2, double* weight);
+/* Preconditioner of the PCG path (no reference counterpart).  The
+ * default is block-Jacobi: the inverses of the diagonal 3x3 blocks.  The chain
+ * preconditioner M follows consecutive rows, which is where odometry edges put
+ * their off-diagonal blocks.  With the rows in the order of
+ * slam_graph_get_system's `times` (nt of them), S the segment length in poses,
+ * D_r the assembled diagonal block of row r and U_r the assembled block (r, r+1)
+ * when that slot exists and floor(r / S) == floor((r + 1) / S), else 0 (a missing
+ * slot, a segment end and the end of the system are the same case):
+ *   M = block-tridiagonal(U_{r-1}^T, D_r, U_r)    (H's own (r+1, r) block is not read)
+ *   factor, once per linearisation:
+ *     S_r = D_r at a segment start, else D_r - U_{r-1}^T G_{r-1}
+ *     Sinv_r = S_r^-1 (the 3x3 LU route of block-Jacobi),  G_r = Sinv_r U_r
+ *   apply z = M^-1 r:
+ *     forward   y_r = r_r - G_{r-1}^T y_{r-1}   (y_r = r_r at a segment start)
+ *     backward  z_r = Sinv_r y_r - G_r z_{r+1}  (z_r = Sinv_r y_r at a segment end)
+ * M is positive semi-definite by construction (an edge between adjacent rows of
+ * one segment is kept whole, of every other edge its two diagonal parts), and it
+ * is algebra on the assembled matrix: pairs only, odometry only, mixed and
+ * robust-weighted systems alike.  S = 1 is block-Jacobi in other arithmetic.
+ *
+ * slam_graph_set_precond: segment must be 1, 2, 4, 8, 16, 32 or 64 (0 means 64;
+ * a PCG workgroup owns 64 whole poses) and is ignored for block-Jacobi.
+ * SLAM_ERR_ARG, checked on the host before the handle changes, for a NULL
+ * handle, an unknown kind and any other segment.  Takes effect at the next
+ * linearisation.  A handle on which it is never called, or called with
+ * block-Jacobi, launches what it launched before the call existed and returns
+ * the same bits.  On the dense path it is accepted and has no effect.  The
+ * condition estimate, the gate and slam_graph_marginals keep block-Jacobi.
+ * When the factor meets a bad pivot (a leading minor of S_r that is not
+ * positive, or a value that is not finite) the solve ends as "not positive
+ * definite" at iteration 0: is_calc = 0 and no error code, the outcome of the
+ * PCG's curvature gate.
+ *
+ * slam_graph_precond_info: out[4] = {kind in force, segment in force (1 for
+ * block-Jacobi), off-diagonal blocks the last factor used, bad pivots}; the
+ * last two are 0 until a chain factor has run on the assembled system.
+ *
+ * slam_graph_apply_precond: z = M^-1 r for a host vector of 3 nt values by the
+ * preconditioner in force on the last assembled system (factored here if no
+ * solve has done it: the dense path, slam_graph_marginals with relinearize =
+ * 1); with block-Jacobi z = minv r.  SLAM_ERR_ARG for a NULL argument and when
+ * nothing has been assembled since slam_graph_set_edges.  It moves no pose and
+ * leaves slam_graph_get_delta, timing, cond_info, gate_info and the warm starts
+ * alone.  For the tests, and for a caller's own Krylov method on
+ * slam_graph_get_bsr. */
+#define SLAM_GRAPH_PRECOND_BLOCK_JACOBI 0
+#define SLAM_GRAPH_PRECOND_CHAIN        1
+int slam_graph_set_precond(slam_graph* h, int32_t kind, int32_t segment);
+int slam_graph_precond_info(slam_graph* h, double* out /* [4] */);
+int slam_graph_apply_precond(slam_graph* h, const double* r, double* z);
 /* HalfEdge (graph_based_slam.py:259-300) with its Observation (:20-75). */
 typedef struct {
     int64_t time, pose, landmark;

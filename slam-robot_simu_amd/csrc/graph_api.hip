@@ -96,6 +96,13 @@ struct slam_graph {
     DeviceMem robust;
     double* rw = nullptr;
     int64_t rw_cap = 0;            // edges rw was sized for
+    // preconditioner of the PCG path (slam_graph_set_precond): the
+    // request, and what the last linearisation latched (in force)
+    int32_t precond_kind = SLAM_GRAPH_PRECOND_BLOCK_JACOBI, precond_seg = 64;
+    int32_t pc_kind = SLAM_GRAPH_PRECOND_BLOCK_JACOBI, pc_seg = 1;
+    bool pc_ready = false;         // minv (and fac) hold the factors of the assembled system
+    double* fac = nullptr;         // [nt][18]: Sinv, G of the chain factor
+    int32_t* pc_cnt = nullptr;     // [0] off-diagonal blocks used, [1] bad pivots
 };
 
 namespace {
@@ -178,6 +185,8 @@ int carve_edge_set(slam_graph* h, int64_t E, int64_t nt_ub, size_t tmp_bytes, Bu
                                       (int64_t)nblk(K, kCertThreads) + 8);
         h->cert = c.take<CertState>(1);
         h->luout = c.take<double>(8);
+        h->fac = c.take<double>(kChainFac * nt_ub);
+        h->pc_cnt = c.take<int32_t>(2);
         if (bs) {
             bs->tl = c.take<int64_t>(2 * E);
             bs->tl_s = c.take<int64_t>(2 * E);
@@ -534,6 +543,10 @@ int launch_linearize(slam_graph* h) {
         hipLaunchKernelGGL(graph_linearize_odom_kernel, dim3(nblk(n_od)), dim3(256), 0, h->stream,
                            h->E_lm, h->E, h->edges, h->poses, h->blocks, rows);
     h->lin_kind = kind;
+    // the preconditioner takes effect here, like the robust kind
+    h->pc_kind = h->precond_kind;
+    h->pc_seg = (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN) ? h->precond_seg : 1;
+    h->pc_ready = false;
     return SLAM_OK;
 }
 
@@ -877,7 +890,24 @@ int cert_gate(slam_graph* h, const CondState& cs, double* stats, bool* gate) {
     return SLAM_OK;
 }
 
-// PCG on H delta = -b with block-Jacobi (large trajectories): two launches per
+// The factors of the preconditioner in force on the assembled system: the
+// block-Jacobi inverses always (the condition estimate and the gate use them),
+// the chain factor beside them when it is in force.
+int precond_factor(slam_graph* h) {
+    hipLaunchKernelGGL(graph_block_inv_kernel, dim3(nblk(h->nt)), dim3(256), 0, h->stream, h->nt,
+                       h->dslot, h->val, h->minv);
+    if (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN) {
+        SLAM_HIP_TRY(hipMemsetAsync(h->pc_cnt, 0, 2 * sizeof(int32_t), h->stream));
+        const int64_t nseg = (h->nt + h->pc_seg - 1) / h->pc_seg;
+        hipLaunchKernelGGL(graph_chain_factor_kernel, dim3(nblk(nseg, 64)), dim3(64), 0, h->stream,
+                           h->nt, h->pc_seg, h->rptr, h->scol, h->dslot, h->val, h->fac, h->pc_cnt);
+    }
+    h->pc_ready = true;
+    return SLAM_OK;
+}
+
+// PCG on H delta = -b with block-Jacobi, or with the chain preconditioner when
+// slam_graph_set_precond put it in force (large trajectories): two launches per
 // iteration, enqueued in chunks between host polls of the device state.  The
 // gate's condition number (:495) is estimated on a second stream at the same
 // time (cond_mode SLAM_GRAPH_COND_ESTIMATE); the solve is applied only if the
@@ -887,16 +917,21 @@ int solve_pcg(slam_graph* h, double* stats, bool* solved, int32_t* iters) {
     const unsigned nb = nblk(n, kPcgThreads);
     const bool cert = (h->cfg.cond_mode == SLAM_GRAPH_COND_MARGIN);
     const bool est = (h->cfg.cond_mode == SLAM_GRAPH_COND_ESTIMATE) || cert;   // the estimate runs
-    hipLaunchKernelGGL(graph_block_inv_kernel, dim3(nblk(h->nt)), dim3(256), 0, h->stream, h->nt,
-                       h->dslot, h->val, h->minv);
+    const bool chain = (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN);
+    GTRY(precond_factor(h));
     if (est) {
         SLAM_HIP_TRY(hipEventRecord(h->cev[0], h->stream));
         SLAM_HIP_TRY(hipStreamWaitEvent(h->cstream, h->cev[0], 0));
         SLAM_HIP_TRY(hipEventRecord(h->cev[1], h->cstream));
     }
     if (cert) GTRY(cert_enqueue(h));
-    hipLaunchKernelGGL(graph_pcg_start_kernel, dim3(nb), dim3(kPcgThreads), 0, h->stream, n,
-                       h->minv, h->b, h->delta, h->r, h->z, h->part);
+    if (chain)
+        hipLaunchKernelGGL(graph_pcg_start_kernel<true>, dim3(nb), dim3(kPcgThreads), 0, h->stream, n,
+                           h->minv, h->b, h->delta, h->r, h->z, h->part, h->fac, h->pc_seg,
+                           h->pc_cnt);
+    else
+        hipLaunchKernelGGL(graph_pcg_start_kernel<false>, dim3(nb), dim3(kPcgThreads), 0, h->stream,
+                           n, h->minv, h->b, h->delta, h->r, h->z, h->part, nullptr, 0, nullptr);
     SLAM_HIP_TRY(hipGetLastError());
     PcgState& s = *h->pcg_host;
     CondState& cs = *h->cond_host;
@@ -924,8 +959,14 @@ int solve_pcg(slam_graph* h, double* stats, bool* solved, int32_t* iters) {
                 hipLaunchKernelGGL(graph_pcg_dir_spmv_kernel, dim3(nb), dim3(kSpmvThreads), 0,
                                    h->stream, h->nt, k, h->rptr, h->scol, h->val, h->z, h->p, h->q,
                                    h->part, h->st, h->cfg.pcg_tol, h->cfg.pcg_max_iter);
-                hipLaunchKernelGGL(graph_pcg_step_kernel, dim3(nb), dim3(kPcgThreads), 0, h->stream,
-                                   n, k, h->minv, h->p, h->q, h->delta, h->r, h->z, h->part, h->st);
+                if (chain)
+                    hipLaunchKernelGGL(graph_pcg_step_kernel<true>, dim3(nb), dim3(kPcgThreads), 0,
+                                       h->stream, n, k, h->minv, h->p, h->q, h->delta, h->r, h->z,
+                                       h->part, h->st, h->fac, h->pc_seg);
+                else
+                    hipLaunchKernelGGL(graph_pcg_step_kernel<false>, dim3(nb), dim3(kPcgThreads), 0,
+                                       h->stream, n, k, h->minv, h->p, h->q, h->delta, h->r, h->z,
+                                       h->part, h->st, nullptr, 0);
                 ++ip;
             }
         }
@@ -1471,6 +1512,59 @@ int slam_graph_set_robust(slam_graph* h, int32_t kind, double param) {
                    "slam_graph_set_robust: the parameter of huber, cauchy and dcs must be > 0");
     h->robust_kind = kind;
     h->robust_param = param;
+    return SLAM_OK;
+}
+
+int slam_graph_set_precond(slam_graph* h, int32_t kind, int32_t segment) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_precond: NULL handle");
+    SLAM_ARG_CHECK(kind == SLAM_GRAPH_PRECOND_BLOCK_JACOBI || kind == SLAM_GRAPH_PRECOND_CHAIN,
+                   "slam_graph_set_precond: unknown kind");
+    if (kind == SLAM_GRAPH_PRECOND_CHAIN) {
+        if (segment == 0) segment = kChainPoses;
+        SLAM_ARG_CHECK(segment >= 1 && segment <= kChainPoses && (segment & (segment - 1)) == 0,
+                       "slam_graph_set_precond: segment must be 0, 1, 2, 4, 8, 16, 32 or 64");
+        h->precond_seg = segment;
+    }
+    h->precond_kind = kind;
+    return SLAM_OK;
+}
+
+int slam_graph_precond_info(slam_graph* h, double* out) {
+    SLAM_ARG_CHECK(h && out, "slam_graph_precond_info: NULL argument");
+    out[0] = h->pc_kind;
+    out[1] = h->pc_seg;
+    out[2] = out[3] = 0.0;
+    if (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN && h->pc_ready && h->assembled) {
+        SLAM_HIP_TRY(hipSetDevice(h->device));
+        int32_t cnt[2];
+        SLAM_HIP_TRY(hipMemcpyAsync(cnt, h->pc_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+        SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+        out[2] = cnt[0];
+        out[3] = cnt[1];
+    }
+    return SLAM_OK;
+}
+
+int slam_graph_apply_precond(slam_graph* h, const double* r, double* z) {
+    SLAM_ARG_CHECK(h && r && z, "slam_graph_apply_precond: NULL argument");
+    SLAM_ARG_CHECK(h->assembled && h->nt > 0,
+                   "slam_graph_apply_precond: no system assembled since slam_graph_set_edges");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    const int64_t n = 3 * h->nt;
+    const unsigned nb = nblk(n, kPcgThreads);
+    hipStream_t s = h->stream;
+    if (!h->pc_ready) GTRY(precond_factor(h));
+    // the PCG's own r and z are scratch between solves
+    SLAM_HIP_TRY(hipMemcpyAsync(h->r, r, n * sizeof(double), hipMemcpyHostToDevice, s));
+    if (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN)
+        hipLaunchKernelGGL(graph_precond_apply_kernel<true>, dim3(nb), dim3(kPcgThreads), 0, s, n,
+                           h->minv, h->fac, h->pc_seg, h->r, h->z);
+    else
+        hipLaunchKernelGGL(graph_precond_apply_kernel<false>, dim3(nb), dim3(kPcgThreads), 0, s, n,
+                           h->minv, h->fac, h->pc_seg, h->r, h->z);
+    SLAM_HIP_TRY(hipGetLastError());
+    SLAM_HIP_TRY(hipMemcpyAsync(z, h->z, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
     return SLAM_OK;
 }
 

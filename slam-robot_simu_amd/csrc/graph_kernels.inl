@@ -12,7 +12,8 @@
 //     re-orthogonalisation, the reference's gate (0.1 < det, cond < 1e15),
 //     and delta = -H^-1 b by the LU factors;
 //   * PCG on the 3x3 block-sparse H with a block-Jacobi preconditioner (large
-//     trajectories, BASELINE config 5): det and cond are not formed.
+//     trajectories, BASELINE config 5): det and cond are not formed.  Opt-in:
+//     the chain preconditioner along consecutive poses.
 #pragma once
 
 #include "common.hpp"
@@ -833,11 +834,110 @@ __device__ __forceinline__ double pcg_fold(const double* __restrict__ part, cons
 
 __device__ __forceinline__ bool pcg_lead() { return blockIdx.x == 0 && threadIdx.x == 0; }
 
-// x = 0, r = -b, z = M^-1 r ; partials r.z, r.r
+// ---- chain preconditioner (SLAM_GRAPH_PRECOND_CHAIN of slam_hip.h)
+// M is the block-tridiagonal part of H in row order, cut every `seg` poses
+// (seg in {1, 2, 4, .. 64}: a segment never crosses a workgroup's 64 poses).
+// graph_chain_factor_kernel leaves 18 doubles per pose: Sinv_r (the inverse of
+// the pivot S_r = D_r - U_{r-1}^T G_{r-1}) and G_r = Sinv_r U_r (zero where M
+// has no (r, r+1) block: a missing slot, a segment end, the end of the system).
+constexpr int kChainPoses = kPcgThreads / 3;          // poses of one PCG workgroup
+constexpr int kChainFac = 18;                         // doubles per pose: Sinv, G
+constexpr int kChainLoads = kChainPoses * kChainFac / kPcgThreads;      // per lane
+static_assert(kChainLoads * kPcgThreads == kChainPoses * kChainFac, "whole loads per lane");
+
+// the workgroup's factors: global -> registers (issued early, under a fold) ...
+__device__ __forceinline__ void chain_load(const double* __restrict__ fac, const int64_t n,
+                                           double* f) {
+    const int64_t base = (int64_t)blockIdx.x * (kChainPoses * kChainFac) + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < kChainLoads; ++j) {
+        const int64_t t = base + j * kPcgThreads;
+        f[j] = (t < 6 * n) ? fac[t] : 0.0;            // 18 nt = 6 n values in all
+    }
+}
+
+// ... -> LDS (fs: kChainPoses * kChainFac doubles)
+__device__ __forceinline__ void chain_stage(const double* f, double* fs) {
+#pragma unroll
+    for (int j = 0; j < kChainLoads; ++j) fs[threadIdx.x + j * kPcgThreads] = f[j];
+}
+
+// z = M^-1 r of the workgroup's np poses, in place on rs (3 np values), one lane
+// per segment:
+//   forward   y_r = r_r - G_{r-1}^T y_{r-1}        (y_r = r_r at a segment start)
+//   backward  z_r = Sinv_r y_r - G_r z_{r+1}       (z_r = Sinv_r y_r at a segment end)
+// The caller synchronises before (rs, fs written) and after (rs read).
+__device__ __forceinline__ void chain_solve(double* rs, const double* fs, const int seg,
+                                            const int np) {
+    const int r0 = (int)threadIdx.x * seg;
+    if (r0 >= np) return;
+    const int r1 = min(r0 + seg, np);
+    double y0 = rs[3 * r0], y1 = rs[3 * r0 + 1], y2 = rs[3 * r0 + 2];
+    for (int r = r0 + 1; r < r1; ++r) {
+        const double* G = fs + kChainFac * (r - 1) + 9;
+        double t0 = fma(-G[0], y0, rs[3 * r]);
+        double t1 = fma(-G[1], y0, rs[3 * r + 1]);
+        double t2 = fma(-G[2], y0, rs[3 * r + 2]);
+        t0 = fma(-G[3], y1, t0);
+        t1 = fma(-G[4], y1, t1);
+        t2 = fma(-G[5], y1, t2);
+        y0 = fma(-G[6], y2, t0);
+        y1 = fma(-G[7], y2, t1);
+        y2 = fma(-G[8], y2, t2);
+        rs[3 * r] = y0;
+        rs[3 * r + 1] = y1;
+        rs[3 * r + 2] = y2;
+    }
+    double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+    for (int r = r1 - 1; r >= r0; --r) {
+        const double* Si = fs + kChainFac * r;
+        const double* G = Si + 9;
+        const double v0 = rs[3 * r], v1 = rs[3 * r + 1], v2 = rs[3 * r + 2];
+        double t0 = Si[0] * v0, t1 = Si[3] * v0, t2 = Si[6] * v0;
+        t0 = fma(Si[1], v1, t0);
+        t1 = fma(Si[4], v1, t1);
+        t2 = fma(Si[7], v1, t2);
+        t0 = fma(Si[2], v2, t0);
+        t1 = fma(Si[5], v2, t1);
+        t2 = fma(Si[8], v2, t2);
+        if (r < r1 - 1) {
+            t0 = fma(-G[0], z0, t0);
+            t1 = fma(-G[3], z0, t1);
+            t2 = fma(-G[6], z0, t2);
+            t0 = fma(-G[1], z1, t0);
+            t1 = fma(-G[4], z1, t1);
+            t2 = fma(-G[7], z1, t2);
+            t0 = fma(-G[2], z2, t0);
+            t1 = fma(-G[5], z2, t1);
+            t2 = fma(-G[8], z2, t2);
+        }
+        z0 = t0;
+        z1 = t1;
+        z2 = t2;
+        rs[3 * r] = z0;
+        rs[3 * r + 1] = z1;
+        rs[3 * r + 2] = z2;
+    }
+}
+
+// poses of this workgroup (n = 3 nt unknowns)
+__device__ __forceinline__ int chain_poses(const int64_t n) {
+    const int64_t left = n / 3 - (int64_t)blockIdx.x * kChainPoses;
+    return (int)(left < kChainPoses ? left : kChainPoses);
+}
+
+// x = 0, r = -b, z = M^-1 r ; partials r.z, r.r.  CHAIN: M is the chain
+// preconditioner (fac, seg) and minv is not read; when the factor counted a bad
+// pivot (cnt[1] != 0: M is not positive definite) z = 0, so iteration 0 has
+// p = 0, p.q = 0 and its curvature gate ends the solve as "not positive
+// definite" (status 2) before any x is formed.  The default instantiation
+// reads none of the three last arguments.
+template <bool CHAIN = false>
 __global__ __launch_bounds__(kPcgThreads) void graph_pcg_start_kernel(
     const int64_t n, const double* __restrict__ minv, const double* __restrict__ b,
     double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
-    double* __restrict__ part) {
+    double* __restrict__ part, const double* __restrict__ fac, const int32_t seg,
+    const int32_t* __restrict__ cnt) {
     __shared__ double sh[2 * kPcgThreads / 64];
     __shared__ double rs[kPcgThreads];
     const int64_t nb = gridDim.x;
@@ -849,18 +949,35 @@ __global__ __launch_bounds__(kPcgThreads) void graph_pcg_start_kernel(
         x[i] = 0.0;
     }
     rs[threadIdx.x] = ri;
-    __syncthreads();
     double rz = 0.0, rr = 0.0;
-    if (i < n) {
-        const int a = (int)(i % 3);
-        const double* m = minv + (i - a) * 3 + 3 * a;
-        const double* rb = rs + threadIdx.x - a;
-        double zi = m[0] * rb[0];
-        zi = fma(m[1], rb[1], zi);
-        zi = fma(m[2], rb[2], zi);
-        z[i] = zi;
-        rz = zi * ri;
-        rr = ri * ri;
+    if constexpr (CHAIN) {
+        __shared__ double fs[kChainPoses * kChainFac];
+        double f[kChainLoads];
+        chain_load(fac, n, f);
+        chain_stage(f, fs);
+        const bool bad = cnt[1] != 0;
+        __syncthreads();
+        chain_solve(rs, fs, seg, chain_poses(n));
+        __syncthreads();
+        if (i < n) {
+            const double zi = bad ? 0.0 : rs[threadIdx.x];
+            z[i] = zi;
+            rz = zi * ri;
+            rr = ri * ri;
+        }
+    } else {
+        __syncthreads();
+        if (i < n) {
+            const int a = (int)(i % 3);
+            const double* m = minv + (i - a) * 3 + 3 * a;
+            const double* rb = rs + threadIdx.x - a;
+            double zi = m[0] * rb[0];
+            zi = fma(m[1], rb[1], zi);
+            zi = fma(m[2], rb[2], zi);
+            z[i] = zi;
+            rz = zi * ri;
+            rr = ri * ri;
+        }
     }
     block_sum2_fixed<kPcgThreads>(rz, rr, sh);
     if (threadIdx.x == 0) {
@@ -958,12 +1075,16 @@ __global__ __launch_bounds__(kSpmvThreads) void graph_pcg_dir_spmv_kernel(
 }
 
 // iteration k, second launch: alpha = rho_k / p.q (curvature gate), x += alpha p,
-// r -= alpha q, z = M^-1 r ; partials r.z, r.r
+// r -= alpha q, z = M^-1 r ; partials r.z, r.r.  CHAIN: the segment solve on rs
+// in place of the three-FMA minv product; the workgroup's factors are loaded
+// under the p.q fold like the own operands.  The default instantiation reads
+// neither of the two last arguments.
+template <bool CHAIN = false>
 __global__ __launch_bounds__(kPcgThreads) void graph_pcg_step_kernel(
     const int64_t n, const int32_t k, const double* __restrict__ minv,
     const double* __restrict__ p, const double* __restrict__ q, double* __restrict__ x,
     double* __restrict__ r, double* __restrict__ z, double* __restrict__ part,
-    PcgState* __restrict__ st) {
+    PcgState* __restrict__ st, const double* __restrict__ fac, const int32_t seg) {
     __shared__ double sh[2 * kPcgThreads / 64];
     __shared__ double rs[kPcgThreads];
     // own operands first: their loads run under the p.q fold
@@ -974,12 +1095,16 @@ __global__ __launch_bounds__(kPcgThreads) void graph_pcg_step_kernel(
         ri = r[i];
         pi = p[i];
         qi = q[i];
-        const int a = (int)(i % 3);
-        const double* m = minv + (i - a) * 3 + 3 * a;
-        m0 = m[0];
-        m1 = m[1];
-        m2 = m[2];
+        if constexpr (!CHAIN) {
+            const int a = (int)(i % 3);
+            const double* m = minv + (i - a) * 3 + 3 * a;
+            m0 = m[0];
+            m1 = m[1];
+            m2 = m[2];
+        }
     }
+    double f[kChainLoads];          // CHAIN only
+    if constexpr (CHAIN) chain_load(fac, n, f);
     if (st->done) return;
     const int64_t nb = gridDim.x;
     const double pq = pcg_fold(part, nb, sh);
@@ -997,16 +1122,30 @@ __global__ __launch_bounds__(kPcgThreads) void graph_pcg_step_kernel(
         r[i] = ri;
     }
     rs[threadIdx.x] = ri;
-    __syncthreads();
     double rz = 0.0, rr = 0.0;
-    if (i < n) {
-        const double* rb = rs + threadIdx.x - (int)(i % 3);
-        double zi = m0 * rb[0];
-        zi = fma(m1, rb[1], zi);
-        zi = fma(m2, rb[2], zi);
-        z[i] = zi;
-        rz = zi * ri;
-        rr = ri * ri;
+    if constexpr (CHAIN) {
+        __shared__ double fs[kChainPoses * kChainFac];
+        chain_stage(f, fs);
+        __syncthreads();
+        chain_solve(rs, fs, seg, chain_poses(n));
+        __syncthreads();
+        if (i < n) {
+            const double zi = rs[threadIdx.x];
+            z[i] = zi;
+            rz = zi * ri;
+            rr = ri * ri;
+        }
+    } else {
+        __syncthreads();
+        if (i < n) {
+            const double* rb = rs + threadIdx.x - (int)(i % 3);
+            double zi = m0 * rb[0];
+            zi = fma(m1, rb[1], zi);
+            zi = fma(m2, rb[2], zi);
+            z[i] = zi;
+            rz = zi * ri;
+            rr = ri * ri;
+        }
     }
     block_sum2_fixed<kPcgThreads>(rz, rr, sh);
     if (threadIdx.x == 0) {
@@ -1624,6 +1763,97 @@ __global__ __launch_bounds__(256) void graph_block_inv_kernel(const int64_t nb,
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
     inv3_lu(val + dslot[b] * 9, minv + b * 9);
+}
+
+// chain preconditioner: the factors of M, one lane per segment --
+// sequential inside a segment, parallel over segments -- into fac ([nt][18]:
+// Sinv_r, G_r).  U_r is the assembled (r, r+1) block: the slots of a row are
+// sorted by column, so it is the slot behind the diagonal one or it does not
+// exist; M's lower blocks are U_r^T (H's own (r+1, r) block is not read).
+//   S_r = D_r (segment start), else D_r - U_{r-1}^T G_{r-1};   Sinv_r = S_r^-1
+//   (inv3_lu, the route of graph_block_inv_kernel);   G_r = Sinv_r U_r
+// cnt[0] += off-diagonal blocks used; cnt[1] += bad pivots: a leading minor of
+// S_r that is not positive, or any value of S_r that is not finite.
+__global__ __launch_bounds__(64) void graph_chain_factor_kernel(
+    const int64_t nt, const int32_t seg, const int64_t* __restrict__ rptr,
+    const int64_t* __restrict__ col, const int64_t* __restrict__ dslot,
+    const double* __restrict__ val, double* __restrict__ fac, int32_t* __restrict__ cnt) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r0 = g * seg;
+    if (r0 >= nt) return;
+    const int64_t r1 = (r0 + seg < nt) ? r0 + seg : nt;
+    double Up[9], Gp[9];                 // U_{r-1}, G_{r-1}
+    int32_t used = 0, bad = 0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t d = dslot[r];
+        double S[9], Si[9], U[9], G[9];
+#pragma unroll
+        for (int q = 0; q < 9; ++q) S[q] = val[d * 9 + q];
+        if (r > r0) {
+            double T[9];
+            mat3_tmul(Up, Gp, T);
+#pragma unroll
+            for (int q = 0; q < 9; ++q) S[q] -= T[q];
+        }
+        const double m2 = S[0] * S[4] - S[1] * S[3];
+        const double m3 = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) +
+                          S[2] * (S[3] * S[7] - S[4] * S[6]);
+        bool ok = S[0] > 0.0 && m2 > 0.0 && m3 > 0.0;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) ok = ok && isfinite(S[q]);
+        if (!ok) ++bad;
+        inv3_lu(S, Si);
+        const bool has = r + 1 < r1 && d + 1 < rptr[r + 1] && col[d + 1] == r + 1;
+        if (has) {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) U[q] = val[(d + 1) * 9 + q];
+            mat3_mul(Si, U, G);
+            ++used;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 9; ++q) U[q] = G[q] = 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            fac[r * kChainFac + q] = Si[q];
+            fac[r * kChainFac + 9 + q] = G[q];
+            Up[q] = U[q];
+            Gp[q] = G[q];
+        }
+    }
+    if (used) atomicAdd(cnt, used);
+    if (bad) atomicAdd(cnt + 1, bad);
+}
+
+// z = M^-1 r by the preconditioner in force (slam_graph_apply_precond): the
+// statements of graph_pcg_start_kernel on a caller's vector, nothing else written.
+template <bool CHAIN>
+__global__ __launch_bounds__(kPcgThreads) void graph_precond_apply_kernel(
+    const int64_t n, const double* __restrict__ minv, const double* __restrict__ fac,
+    const int32_t seg, const double* __restrict__ r, double* __restrict__ z) {
+    __shared__ double rs[kPcgThreads];
+    const int64_t i = (int64_t)blockIdx.x * kPcgThreads + threadIdx.x;
+    rs[threadIdx.x] = (i < n) ? r[i] : 0.0;
+    if constexpr (CHAIN) {
+        __shared__ double fs[kChainPoses * kChainFac];
+        double f[kChainLoads];
+        chain_load(fac, n, f);
+        chain_stage(f, fs);
+        __syncthreads();
+        chain_solve(rs, fs, seg, chain_poses(n));
+        __syncthreads();
+        if (i < n) z[i] = rs[threadIdx.x];
+    } else {
+        __syncthreads();
+        if (i < n) {
+            const int a = (int)(i % 3);
+            const double* m = minv + (i - a) * 3 + 3 * a;
+            const double* rb = rs + threadIdx.x - a;
+            double zi = m[0] * rb[0];
+            zi = fma(m[1], rb[1], zi);
+            z[i] = fma(m[2], rb[2], zi);
+        }
+    }
 }
 
 // ------------------------------------------------------- pose update

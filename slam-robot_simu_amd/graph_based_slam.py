@@ -232,6 +232,13 @@ class TrajectoryEstimator(object):
                 raise ValueError("odometry sigma must be three finite values > 0")
         self._odom_sigma = sigma
 
+    def setPrecond(self, precond):
+        """Preconditioner of the device's PCG path: None /
+        "block_jacobi" (the default), "chain" or ("chain", S); see
+        DeviceGraph.set_precond.  No effect below 2048 unknowns under
+        ``solver="auto"`` (the dense path)."""
+        self._dev.set_precond(precond)
+
     def addPose(self, aPose, aIsObs, aOdom=None):
         """``aOdom``: the relative motion (relpose) of the step that led to this
         pose, kept for the odometry edges."""

@@ -121,6 +121,7 @@ class GraphConfig(C.Structure):
 GRAPH_SOLVER = {"auto": 0, "dense": 1, "pcg": 2}
 GRAPH_COND = {"estimate": 0, "off": 1, "margin": 2, "certify": 2}   # "certify": the former name
 GRAPH_ROBUST = {"none": 0, "huber": 1, "cauchy": 2, "dcs": 3}        # SLAM_GRAPH_ROBUST_*
+GRAPH_PRECOND = {"block_jacobi": 0, "chain": 1}                      # SLAM_GRAPH_PRECOND_*
 
 _P = C.c_void_p
 _D = C.POINTER(C.c_double)
@@ -300,6 +301,9 @@ SIGNATURES = {
     "slam_graph_set_robust": (C.c_int, [_P, C.c_int32, C.c_double]),
     "slam_graph_chi2": (C.c_int, [_P, _D, _D, _D]),
     "slam_graph_get_edge_weights": (C.c_int, [_P, _D, _D]),
+    "slam_graph_set_precond": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "slam_graph_precond_info": (C.c_int, [_P, _D]),
+    "slam_graph_apply_precond": (C.c_int, [_P, _D, _D]),
     "slam_graph_linearize_solve": (C.c_int, [C.POINTER(GraphConfig), _P, C.c_int64, _D, C.c_int64,
                                              _D, C.c_int]),
     "slam_graph_pair_halves": (C.c_int, [C.c_int64, _P, C.c_int64, C.c_int, _I64, _P]),

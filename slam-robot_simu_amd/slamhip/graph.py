@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import GRAPH_COND, GRAPH_ROBUST, GRAPH_SOLVER, GraphConfig, check, dptr
+from ._lib import GRAPH_COND, GRAPH_PRECOND, GRAPH_ROBUST, GRAPH_SOLVER, GraphConfig, check, dptr
 
 # slam_graph_edge, 80 bytes
 EDGE_DTYPE = np.dtype([("time_bfr", "<i8"), ("pose_bfr", "<i8"), ("time_aft", "<i8"),
@@ -133,6 +133,47 @@ class DeviceGraph:
         check(self._lib.slam_graph_set_robust(self._h, GRAPH_ROBUST[kind],
                                               0.0 if param is None else float(param)),
               "slam_graph_set_robust")
+
+    def set_precond(self, kind, segment=None):
+        """Preconditioner of the PCG path (slam_graph_set_precond):
+        None / "block_jacobi" (the default), "chain", or ("chain", S) with the
+        segment length S in 1, 2, 4 .. 64 poses (``segment``, or 0 / None: 64).
+        Takes effect at the next linearisation; no effect on the dense path."""
+        if isinstance(kind, (tuple, list)):
+            if len(kind) != 2 or segment is not None:
+                raise ValueError("precond must be a kind or (kind, segment)")
+            kind, segment = kind
+        kind = "block_jacobi" if kind is None else kind
+        if kind not in GRAPH_PRECOND:
+            raise ValueError("precond kind must be one of %s" % (sorted(GRAPH_PRECOND),))
+        check(self._lib.slam_graph_set_precond(self._h, GRAPH_PRECOND[kind],
+                                               0 if segment is None else int(segment)),
+              "slam_graph_set_precond")
+
+    def precond_info(self):
+        """The preconditioner the last linearisation put in force
+        (slam_graph_precond_info): kind, segment (1 for block-Jacobi), and of the
+        last chain factor the off-diagonal blocks it used and its bad pivots."""
+        out = np.zeros(4)
+        check(self._lib.slam_graph_precond_info(self._h, dptr(out)), "slam_graph_precond_info")
+        names = {v: k for k, v in GRAPH_PRECOND.items()}
+        return dict(kind=names[int(out[0])], segment=int(out[1]), off_diagonal_blocks=int(out[2]),
+                    bad_pivots=int(out[3]))
+
+    def apply_precond(self, r):
+        """z = M^-1 r by the preconditioner in force on the last assembled system
+        (slam_graph_apply_precond): ``r`` has 3 nt values in the order of
+        get_system's times.  Moves nothing."""
+        nt = C.c_int64(0)
+        check(self._lib.slam_graph_get_system(self._h, C.byref(nt), None, None, None, None),
+              "slam_graph_get_system")
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        if len(r) != 3 * nt.value:
+            raise ValueError("r must have 3 nt = %d values" % (3 * nt.value,))
+        z = np.empty(len(r))
+        check(self._lib.slam_graph_apply_precond(self._h, dptr(r), dptr(z)),
+              "slam_graph_apply_precond")
+        return z
 
     def chi2(self, per_edge=False):
         """Chi-square of the edge set at the current poses under the handle's
