@@ -1037,6 +1037,61 @@ int slam_graph_update(slam_graph* h, double* stats);
  * SLAM_ERR_SOLVE (with *n_iter set) when a PCG solve fails to converge. */
 int slam_graph_optimize(slam_graph* h, double delta_sum_th, int32_t max_iter, double* stats,
                         int32_t* n_iter);
+/* Members (no reference counterpart): many graphs of the dense
+ * path's size in one handle, advanced together with one launch per phase.
+ * Members are disjoint contiguous ranges of the handle's poses: member m holds
+ * poses [pose_off[m], pose_off[m + 1]).  Each is a graph of its own, with its
+ * own anchor (on the first of its times), gate, dense solve, sum delta^2 and
+ * stopping iteration.  The contract: member m is bit for bit what a stand-alone
+ * handle with the same slam_graph_config and robust kind returns that is given
+ * member m's poses and member m's edges alone (its landmark pairs in their
+ * order, then its odometry edges in theirs) -- the poses, every stats row, the
+ * iteration count, delta, the assembled H and b and the edge weights --
+ * whatever the other members are, however many there are and in whatever
+ * order they stand.
+ *
+ * slam_graph_set_members: after slam_graph_set_poses and before
+ * slam_graph_set_edges(_odom).  pose_off[0] = 0, pose_off[n_members] = the
+ * pose count, the offsets increase strictly, no member has more than 682 poses
+ * (2046 unknowns: the dense path's limit), and the handle's solver is not
+ * SLAM_GRAPH_PCG.  n_members = 0 returns the handle to the plain form.  The
+ * call clears the edge set; slam_graph_set_poses clears the members and their
+ * edge set.
+ *
+ * slam_graph_set_edges(_odom) on a handle with members additionally requires
+ * both pose indices and both times of every edge in one member's range (times
+ * index poses).  The columns of the union are all landmark pairs, then all
+ * odometry edges, as ever; within each group a member's edges keep their
+ * relative order, need not be contiguous, and the members need not come in
+ * order.  slam_graph_get_system, get_bsr, get_delta, get_poses, chi2,
+ * get_edge_weights, set_robust (one kind for the handle) and set_precond
+ * (accepted, without effect) work on the union: H is block diagonal by member,
+ * a member's block rows are the ranks of its times.  get_system's dense H is
+ * limited to 2048 unknowns of the union; get_bsr has no limit.
+ *
+ * Every violation is SLAM_ERR_ARG, found on the host before any HIP call, and
+ * leaves the handle as it was.  On a handle with members slam_graph_update,
+ * slam_graph_optimize, slam_graph_marginals and slam_graph_apply_precond
+ * return SLAM_ERR_ARG (the union with one anchor per member is not the system
+ * they describe), and so do the two calls below on a handle without members.
+ *
+ * slam_graph_update_members: one updateEstPose of every member; stats is
+ * [n_members][4], rows as slam_graph_update's.  A member with no edge or with
+ * a single time gets a zero row; is_calc = 0 in a member is not an error.
+ *
+ * slam_graph_optimize_members: every member runs slam_graph_optimize's loop on
+ * its own sum delta^2 (is_calc = 0 gives 0 and ends that member's loop).
+ * Member m stops after its own n_iter[m] updates; from then on nothing it owns
+ * is written (its poses, its columns of the blocks, its weights, its slots of
+ * H, its rows of b and delta), so every query afterwards shows the system of
+ * its last own update.  stats is [n_members][max_iter][4] or NULL, rows beyond
+ * n_iter[m] zero; n_iter is [n_members].  The call ends when no member is
+ * active. */
+int slam_graph_set_members(slam_graph* h, int64_t n_members, const int64_t* pose_off /* [n_members + 1] */);
+int slam_graph_update_members(slam_graph* h, double* stats /* [n_members][4] */);
+int slam_graph_optimize_members(slam_graph* h, double delta_sum_th, int32_t max_iter,
+                                double* stats /* [n_members][max_iter][4] or NULL */,
+                                int32_t* n_iter /* [n_members] */);
 /* The last assembled system: times (n_times), H (3n_times squared, dense, or
  * NULL), b (3 n_times or NULL), blocks (n_edges x 42: BB, BA, AB, AA, b_B, b_A
  * or NULL).  n_times may be queried with everything else NULL.  n_edges here is

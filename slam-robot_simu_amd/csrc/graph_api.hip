@@ -20,6 +20,7 @@
 #include "graph_kernels.inl"
 #include "graph_build.inl"
 #include "graph_marginals.inl"
+#include "graph_members.inl"
 
 using namespace slam;
 
@@ -103,6 +104,20 @@ struct slam_graph {
     bool pc_ready = false;         // minv (and fac) hold the factors of the assembled system
     double* fac = nullptr;         // [nt][18]: Sinv, G of the chain factor
     int32_t* pc_cnt = nullptr;     // [0] off-diagonal blocks used, [1] bad pivots
+    // members (slam_graph_set_members): B > 0 splits the poses into
+    // B graphs of their own.  The index arrays sit in the arena behind the edge
+    // set's; the dense buffers above then hold every member's, one after another.
+    int64_t B = 0;
+    std::vector<int64_t> pose_off;         // [B + 1]
+    std::vector<GraphMember> members;      // rows and buffer offsets, once the edge set stands
+    int32_t *m_edge = nullptr, *m_slot = nullptr, *m_row = nullptr;   // member of edge / slot / row
+    GraphMember* m_desc = nullptr;
+    int32_t *m_active = nullptr, *m_pass = nullptr;   // [B]: touched by the next update / gate passed
+    double *m_luout = nullptr, *m_dsum = nullptr;     // [B][kMemberOut], [B]
+    int32_t* m_flags_host = nullptr;       // pinned [2 B]: active, pass
+    double* m_out_host = nullptr;          // pinned [B][kMemberOut], then the B sums
+    int64_t m_host_cap = 0;                // members the pinned buffers were sized for
+    int64_t m_dense_cap[4] = {0, 0, 0, 0}; // elements of A / LU / S, V, lan, piv the members hold
 };
 
 namespace {
@@ -205,6 +220,16 @@ int carve_edge_set(slam_graph* h, int64_t E, int64_t nt_ub, size_t tmp_bytes, Bu
             bs->tmp = c.take<char>((int64_t)tmp_bytes);
             bs->tmp_bytes = tmp_bytes;
         }
+        // the members' arrays come last, so no offset above depends on them
+        const int64_t Bm = h->B;
+        h->m_edge = c.take<int32_t>(Bm ? E : 0);
+        h->m_slot = c.take<int32_t>(Bm ? K : 0);
+        h->m_row = c.take<int32_t>(Bm ? nt_ub : 0);
+        h->m_desc = c.take<GraphMember>(Bm);
+        h->m_active = c.take<int32_t>(Bm);
+        h->m_pass = c.take<int32_t>(Bm);
+        h->m_luout = c.take<double>(kMemberOut * Bm);
+        h->m_dsum = c.take<double>(Bm);
         if (pass == 0 && c.off > h->arena_bytes) {
             h->mem.release(h->arena);
             h->arena_bytes = 0;
@@ -221,6 +246,7 @@ int dense_buffers(slam_graph* h, int64_t n) {
     if (n <= h->dense_n && h->A) return SLAM_OK;
     h->dense.clear();
     h->dense_n = 0;
+    for (int64_t& c : h->m_dense_cap) c = 0;
     GTRY(h->dense.alloc(&h->A, n * n));
     GTRY(h->dense.alloc(&h->LU, n * n));
     GTRY(h->dense.alloc(&h->S, n * n));
@@ -239,6 +265,7 @@ int finish_structure(slam_graph* h, int64_t E, int64_t nt, int64_t ns) {
     h->nt = nt;
     h->n_slots = ns;
     const int64_t n = 3 * nt;
+    if (h->B) return SLAM_OK;                  // the members' buffers: members_layout
     if (n <= kGraphDenseMax) {
         GTRY(dense_buffers(h, n));
     } else {
@@ -246,7 +273,77 @@ int finish_structure(slam_graph* h, int64_t E, int64_t nt, int64_t ns) {
         h->A = h->LU = h->S = h->V = h->lan = nullptr;
         h->piv = nullptr;
         h->dense_n = 0;
+        for (int64_t& c : h->m_dense_cap) c = 0;
     }
+    return SLAM_OK;
+}
+
+// member of a pose id / time (members are contiguous ranges of both)
+int64_t member_of(const slam_graph* h, const int64_t t) {
+    return (std::upper_bound(h->pose_off.begin(), h->pose_off.end(), t) - h->pose_off.begin()) - 1;
+}
+
+// After the structure of the union stands: the member index of every edge,
+// block row and slot, every member's rows, and the dense buffers of all members
+// (sums over the members, grow-only).  The union's distinct times are sorted,
+// so a member's rows are the contiguous ranks of its times.
+int members_layout(slam_graph* h, const int64_t n_lm, const slam_graph_edge* ed, const int64_t n_od,
+                   const slam_graph_odom* od) {
+    const int64_t B = h->B;
+    std::vector<int32_t> medge((size_t)h->E), mrow((size_t)h->nt);
+    for (int64_t e = 0; e < n_lm; ++e) medge[e] = (int32_t)member_of(h, ed[e].time_bfr);
+    for (int64_t e = 0; e < n_od; ++e) medge[n_lm + e] = (int32_t)member_of(h, od[e].time_bfr);
+    h->members.assign((size_t)B, GraphMember{});
+    for (int64_t r = 0; r < h->nt; ++r) {
+        const int64_t m = member_of(h, h->times_h[r]);
+        mrow[r] = (int32_t)m;
+        if (h->members[m].rows++ == 0) h->members[m].row0 = r;
+    }
+    int64_t need[4] = {0, 0, 0, 0};
+    for (GraphMember& g : h->members) {
+        g.n = (3 * g.rows > 3) ? 3 * g.rows : 0;         // :469 (leng > 3), as do_update
+        const int64_t n = g.n;
+        g.a_off = need[0];
+        g.v_off = need[1];
+        g.l_off = need[2];
+        g.p_off = need[3];
+        need[0] += n * n;
+        need[1] += n * (n + 1);
+        need[2] += 3 * n + 8;
+        need[3] += std::max<int64_t>(n, 1);
+    }
+    bool fits = h->A != nullptr && h->dense_n == 0;
+    for (int k = 0; k < 4; ++k) fits = fits && need[k] <= h->m_dense_cap[k];
+    if (!fits) {
+        h->dense.clear();
+        h->A = h->LU = h->S = h->V = h->lan = nullptr;
+        h->piv = nullptr;
+        h->dense_n = 0;
+        for (int64_t& c : h->m_dense_cap) c = 0;
+        GTRY(h->dense.alloc(&h->A, need[0]));
+        GTRY(h->dense.alloc(&h->LU, need[0]));
+        GTRY(h->dense.alloc(&h->S, need[0]));
+        GTRY(h->dense.alloc(&h->V, need[1]));
+        GTRY(h->dense.alloc(&h->lan, need[2]));
+        GTRY(h->dense.alloc(&h->piv, need[3]));
+        for (int k = 0; k < 4; ++k) h->m_dense_cap[k] = need[k];
+    }
+    if (h->m_host_cap < B) {
+        h->mem.release(h->m_flags_host);
+        h->mem.release(h->m_out_host);
+        h->m_host_cap = 0;
+        GTRY(h->mem.alloc_pinned(&h->m_flags_host, nullptr, (size_t)(2 * B), hipHostMallocDefault));
+        GTRY(h->mem.alloc_pinned(&h->m_out_host, nullptr, (size_t)((kMemberOut + 1) * B),
+                                 hipHostMallocDefault));
+        h->m_host_cap = B;
+    }
+    GTRY(upload(h, h->m_edge, medge));
+    GTRY(upload(h, h->m_row, mrow));
+    GTRY(upload(h, h->m_desc, h->members));
+    hipLaunchKernelGGL(graph_member_slot_kernel, dim3(nblk(h->n_slots)), dim3(256), 0, h->stream,
+                       h->n_slots, h->srow, h->m_row, h->m_slot);
+    SLAM_HIP_TRY(hipGetLastError());
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));     // the uploads read the vectors until here
     return SLAM_OK;
 }
 
@@ -471,12 +568,30 @@ int set_edge_set(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges, i
                            entry + ": odometry sigma must be finite and > 0");
         }
     }
+    if (h->B) {
+        // both poses and both times of an edge in one member's range (the times
+        // index poses: graph_pose_update_kernel)
+        auto one_member = [&](const int64_t tb, const int64_t pb, const int64_t ta, const int64_t pa) {
+            const int64_t m = member_of(h, tb);
+            const int64_t lo = h->pose_off[m], hi = h->pose_off[m + 1];
+            return lo <= pb && pb < hi && lo <= ta && ta < hi && lo <= pa && pa < hi;
+        };
+        for (int64_t e = 0; e < n_edges; ++e)
+            SLAM_ARG_CHECK(one_member(edges[e].time_bfr, edges[e].pose_bfr, edges[e].time_aft,
+                                      edges[e].pose_aft),
+                           entry + ": an edge whose poses and times are not in one member");
+        for (int64_t e = 0; e < n_odom; ++e)
+            SLAM_ARG_CHECK(one_member(odom[e].time_bfr, odom[e].pose_bfr, odom[e].time_aft,
+                                      odom[e].pose_aft),
+                           entry + ": an odometry edge whose poses and times are not in one member");
+    }
     SLAM_HIP_TRY(hipSetDevice(h->device));
     h->assembled = false;
     h->marg_last_iters = 0;
     h->lin_kind = -1;
     int rc = SLAM_OK;
     if (n_edges + n_odom) rc = build_structure(h, n_edges, edges, n_odom, odom);
+    if (!rc && h->B && n_edges + n_odom) rc = members_layout(h, n_edges, edges, n_odom, odom);
     if (rc || n_edges + n_odom == 0) {
         h->E = h->E_lm = h->nt = h->n_slots = 0;
         h->times_h.clear();
@@ -484,6 +599,19 @@ int set_edge_set(slam_graph* h, int64_t n_edges, const slam_graph_edge* edges, i
     }
     h->E_lm = n_edges;
     return SLAM_OK;
+}
+
+// the handle back in the plain form with no edge set (slam_graph_set_members,
+// and slam_graph_set_poses on a handle with members)
+void clear_members(slam_graph* h) {
+    h->B = 0;
+    h->pose_off.clear();
+    h->members.clear();
+    h->E = h->E_lm = h->nt = h->n_slots = 0;
+    h->times_h.clear();
+    h->assembled = false;
+    h->marg_last_iters = 0;
+    h->lin_kind = -1;
 }
 
 GraphConst gconst(const slam_graph_config& c) { return GraphConst{c.r_dist, c.r_dir, c.r_orient}; }
@@ -592,11 +720,11 @@ int linearize_assemble(slam_graph* h) {
     return SLAM_OK;
 }
 
-int dense_matrix(slam_graph* h) {
+int dense_matrix(slam_graph* h, double* A) {
     const int64_t n = 3 * h->nt;
-    SLAM_HIP_TRY(hipMemsetAsync(h->A, 0, n * n * sizeof(double), h->stream));
+    SLAM_HIP_TRY(hipMemsetAsync(A, 0, n * n * sizeof(double), h->stream));
     hipLaunchKernelGGL(graph_dense_scatter_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0,
-                       h->stream, h->n_slots, h->srow, h->scol, h->val, n, h->A);
+                       h->stream, h->n_slots, h->srow, h->scol, h->val, n, A);
     SLAM_HIP_TRY(hipGetLastError());
     return SLAM_OK;
 }
@@ -604,7 +732,7 @@ int dense_matrix(slam_graph* h) {
 // dense path: LU of H and the reference's gate on it (updateEstPose :494-496)
 int dense_factor_gate(slam_graph* h, double* det_out, double* cond_out, bool* pass) {
     const int64_t n = 3 * h->nt;
-    GTRY(dense_matrix(h));
+    GTRY(dense_matrix(h, h->A));
     SLAM_HIP_TRY(hipMemcpyAsync(h->LU, h->A, n * n * sizeof(double), hipMemcpyDeviceToDevice,
                                 h->stream));
     hipLaunchKernelGGL(graph_symmetrize_kernel, dim3(nblk(n * n)), dim3(256), 0, h->stream, h->A, n,
@@ -746,7 +874,7 @@ int cert_enqueue(slam_graph* h) {
 // det(H) from the dense LU (n <= kGraphDenseMax): the certificate's fallback
 int dense_det(slam_graph* h, double* det) {
     const int64_t n = 3 * h->nt;
-    GTRY(dense_matrix(h));
+    GTRY(dense_matrix(h, h->A));
     SLAM_HIP_TRY(hipMemcpyAsync(h->LU, h->A, n * n * sizeof(double), hipMemcpyDeviceToDevice,
                                 h->stream));
     hipLaunchKernelGGL(graph_lu_kernel, dim3(1), dim3(kGraphThreads), 0, h->stream, h->LU, (int)n,
@@ -762,7 +890,7 @@ int dense_det(slam_graph* h, double* det) {
 // cond(H) by the dense path's Lanczos (n <= kGraphDenseMax): the certificate's fallback
 int dense_cond(slam_graph* h, double* cond) {
     const int64_t n = 3 * h->nt;
-    GTRY(dense_matrix(h));
+    GTRY(dense_matrix(h, h->A));
     hipLaunchKernelGGL(graph_symmetrize_kernel, dim3(nblk(n * n)), dim3(256), 0, h->stream, h->A, n,
                        h->S);
     hipLaunchKernelGGL(graph_lanczos_kernel, dim3(1), dim3(kGraphThreads), 0, h->stream, h->S,
@@ -1076,8 +1204,119 @@ int do_update(slam_graph* h, double* stats) {
     return SLAM_OK;
 }
 
+// ---- members (graph_members.inl)
+// the linearise launches of launch_linearize over the members that are active
+int launch_linearize_members(slam_graph* h) {
+    const int32_t kind = h->robust_kind;
+    const int64_t n_od = h->E - h->E_lm;
+    double* rows = nullptr;
+    if (kind != SLAM_GRAPH_ROBUST_NONE) {
+        GTRY(robust_reserve(h));
+        rows = robust_rows(h).lin;
+    }
+#define SLAM_LINEARIZE_MEMBERS(K)                                                                  \
+    hipLaunchKernelGGL(graph_member_linearize_kernel<K>, dim3(nblk(h->E_lm)), dim3(256), 0,        \
+                       h->stream, h->E_lm, h->E, h->edges, h->poses, gconst(h->cfg), h->blocks,    \
+                       h->robust_param, rows, h->m_edge, h->m_active)
+    if (h->E_lm) switch (kind) {
+            case SLAM_GRAPH_ROBUST_HUBER: SLAM_LINEARIZE_MEMBERS(SLAM_GRAPH_ROBUST_HUBER); break;
+            case SLAM_GRAPH_ROBUST_CAUCHY: SLAM_LINEARIZE_MEMBERS(SLAM_GRAPH_ROBUST_CAUCHY); break;
+            case SLAM_GRAPH_ROBUST_DCS: SLAM_LINEARIZE_MEMBERS(SLAM_GRAPH_ROBUST_DCS); break;
+            default: SLAM_LINEARIZE_MEMBERS(SLAM_GRAPH_ROBUST_NONE); break;
+        }
+#undef SLAM_LINEARIZE_MEMBERS
+    if (n_od)
+        hipLaunchKernelGGL(graph_member_linearize_odom_kernel, dim3(nblk(n_od)), dim3(256), 0,
+                           h->stream, h->E_lm, h->E, h->edges, h->poses, h->blocks, rows, h->m_edge,
+                           h->m_active);
+    h->lin_kind = kind;
+    h->pc_kind = h->precond_kind;                  // accepted, without effect (the dense path)
+    h->pc_seg = (h->pc_kind == SLAM_GRAPH_PRECOND_CHAIN) ? h->precond_seg : 1;
+    h->pc_ready = false;
+    return SLAM_OK;
+}
+
+// One updateEstPose of every member with act[m] != 0, all members per launch;
+// stats [B][4], zero rows for the others and for a member that is never solved.
+// Two synchronisations: the members' LU / Lanczos results for the host's gate
+// (formed as dense_factor_gate forms it), and the sums of delta^2.
+int do_update_members(slam_graph* h, const std::vector<char>& act, double* stats) {
+    const int64_t B = h->B;
+    std::fill(stats, stats + 4 * B, 0.0);
+    for (double& x : h->last) x = 0.0;
+    h->pcg_failed = false;
+    if (h->E == 0) return SLAM_OK;
+    bool any = false;
+    for (int64_t m = 0; m < B; ++m) {
+        h->m_flags_host[m] = (act[m] && h->members[m].n > 0) ? 1 : 0;
+        any = any || h->m_flags_host[m];
+    }
+    if (!any) return SLAM_OK;
+    hipStream_t s = h->stream;
+    const dim3 per_member((unsigned)B), split((unsigned)B, kMemberSplit), wg(kGraphThreads);
+    SLAM_HIP_TRY(hipMemcpyAsync(h->m_active, h->m_flags_host, B * sizeof(int32_t),
+                                hipMemcpyHostToDevice, s));
+    SLAM_HIP_TRY(hipEventRecord(h->ev[0], s));
+    GTRY(launch_linearize_members(h));
+    SLAM_HIP_TRY(hipEventRecord(h->ev[1], s));
+    hipLaunchKernelGGL(graph_member_assemble_h_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0, s,
+                       h->n_slots, h->E, h->cptr, h->clist, h->blocks, h->cfg.anchor, h->val,
+                       h->m_slot, h->m_desc, h->dslot, h->m_active);
+    hipLaunchKernelGGL(graph_member_assemble_b_kernel, dim3(nblk(3 * h->nt)), dim3(256), 0, s,
+                       h->nt, h->E, h->bptr, h->blist, h->blocks, h->b, h->m_row, h->m_active);
+    SLAM_HIP_TRY(hipEventRecord(h->ev[2], s));
+    h->assembled = true;
+    hipLaunchKernelGGL(graph_member_zero_kernel, split, wg, 0, s, h->m_desc, h->m_active, h->A);
+    hipLaunchKernelGGL(graph_member_scatter_kernel, dim3(nblk(9 * h->n_slots)), dim3(256), 0, s,
+                       h->n_slots, h->srow, h->scol, h->val, h->m_slot, h->m_desc, h->m_active, h->A);
+    hipLaunchKernelGGL(graph_member_symmetrize_kernel, split, wg, 0, s, h->m_desc, h->m_active,
+                       h->A, h->S, h->LU);
+    hipLaunchKernelGGL(graph_member_lu_kernel, per_member, wg, 0, s, h->m_desc, h->m_active, h->LU,
+                       h->piv, h->m_luout);
+    hipLaunchKernelGGL(graph_member_lanczos_kernel, per_member, wg, 0, s, h->m_desc, h->m_active,
+                       h->S, h->V, h->lan, h->m_luout, (uint64_t)0x5EEDULL);
+    SLAM_HIP_TRY(hipGetLastError());
+    SLAM_HIP_TRY(hipMemcpyAsync(h->m_out_host, h->m_luout, kMemberOut * B * sizeof(double),
+                                hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
+    int32_t* pass = h->m_flags_host + B;
+    for (int64_t m = 0; m < B; ++m) {
+        pass[m] = 0;
+        if (!h->m_flags_host[m]) continue;
+        // numpy det: sign * exp(logdet); a zero pivot gives 0 (getrf info > 0)
+        const double* lo = h->m_out_host + kMemberOut * m;
+        const double det = (lo[2] != 0.0) ? 0.0 : lo[0] * std::exp(lo[1]);
+        const double cond = (lo[4] > 0.0) ? lo[3] / lo[4] : std::numeric_limits<double>::infinity();
+        stats[4 * m + 2] = det;
+        stats[4 * m + 3] = cond;
+        pass[m] = ((h->cfg.det_min < det) && (cond < h->cfg.cond_max)) ? 1 : 0;
+    }
+    SLAM_HIP_TRY(hipMemcpyAsync(h->m_pass, pass, B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(graph_member_lu_solve_kernel, per_member, wg, 0, s, h->m_desc, h->m_active,
+                       h->m_pass, h->LU, h->piv, h->b, h->delta);
+    SLAM_HIP_TRY(hipEventRecord(h->ev[3], s));
+    hipLaunchKernelGGL(graph_member_pose_update_kernel, per_member, dim3(1024), 0, s, h->m_desc,
+                       h->m_active, h->m_pass, h->times, h->delta, h->poses, h->m_dsum);
+    SLAM_HIP_TRY(hipGetLastError());
+    double* dsum = h->m_out_host + kMemberOut * B;
+    SLAM_HIP_TRY(hipMemcpyAsync(dsum, h->m_dsum, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipEventRecord(h->ev[4], s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t m = 0; m < B; ++m)
+        if (pass[m]) {
+            stats[4 * m] = 1.0;
+            stats[4 * m + 1] = dsum[m];
+        }
+    float ms;
+    for (int k = 0; k < 4; ++k) {
+        SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+        h->last[k] = ms;
+    }
+    return SLAM_OK;
+}
+
 // ---- slam_graph_marginals (graph_marginals.inl)
-constexpr int kMargDefaultCols = 4;     // least time per column at config 5
+constexpr int kMargDefaultCols = 4;    // least time per column at config 5
 constexpr int kMargWidths[] = {1, 2, 4, 8};
 static_assert(kMargDefaultCols <= kMargMaxCols, "MargState holds the widest pass");
 
@@ -1286,6 +1525,7 @@ int slam_graph_destroy(slam_graph* h) {
 int slam_graph_set_poses(slam_graph* h, int64_t n_poses, const double* poses) {
     SLAM_ARG_CHECK(h && poses && n_poses >= 1, "slam_graph_set_poses: bad arguments");
     SLAM_HIP_TRY(hipSetDevice(h->device));
+    if (h->B) clear_members(h);                    // the members go, and their edge set with them
     if (n_poses != h->T) {
         h->mem.release(h->poses);
         h->T = 0;
@@ -1326,6 +1566,7 @@ int slam_graph_set_edges_odom(slam_graph* h, int64_t n_edges, const slam_graph_e
 
 int slam_graph_update(slam_graph* h, double* stats) {
     SLAM_ARG_CHECK(h && stats && h->poses, "slam_graph_update: bad arguments");
+    SLAM_ARG_CHECK(h->B == 0, "slam_graph_update: the handle has members (slam_graph_update_members)");
     SLAM_HIP_TRY(hipSetDevice(h->device));
     return do_update(h, stats);
 }
@@ -1333,6 +1574,8 @@ int slam_graph_update(slam_graph* h, double* stats) {
 int slam_graph_optimize(slam_graph* h, double delta_sum_th, int32_t max_iter, double* stats,
                         int32_t* n_iter) {
     SLAM_ARG_CHECK(h && h->poses && max_iter >= 1, "slam_graph_optimize: bad arguments");
+    SLAM_ARG_CHECK(h->B == 0,
+                   "slam_graph_optimize: the handle has members (slam_graph_optimize_members)");
     SLAM_HIP_TRY(hipSetDevice(h->device));
     int32_t it = 0;
     double s[4] = {0, 0, 0, 0};
@@ -1355,6 +1598,65 @@ int slam_graph_optimize(slam_graph* h, double delta_sum_th, int32_t max_iter, do
     return SLAM_OK;
 }
 
+int slam_graph_set_members(slam_graph* h, int64_t n_members, const int64_t* pose_off) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_members: NULL handle");
+    SLAM_ARG_CHECK(n_members >= 0 && (pose_off || n_members == 0),
+                   "slam_graph_set_members: negative count, or NULL offsets with a positive count");
+    if (n_members) {
+        SLAM_ARG_CHECK(h->poses, "slam_graph_set_members: set the poses first");
+        SLAM_ARG_CHECK(h->cfg.solver != SLAM_GRAPH_PCG,
+                       "slam_graph_set_members: members take the dense path, the handle's solver is PCG");
+        SLAM_ARG_CHECK(n_members <= h->T && pose_off[0] == 0 && pose_off[n_members] == h->T,
+                       "slam_graph_set_members: the offsets must run from 0 to the pose count");
+        for (int64_t m = 0; m < n_members; ++m) {
+            SLAM_ARG_CHECK(pose_off[m] < pose_off[m + 1],
+                           "slam_graph_set_members: the offsets must increase strictly");
+            SLAM_ARG_CHECK(pose_off[m + 1] - pose_off[m] <= kGraphDenseMax / 3,
+                           "slam_graph_set_members: a member is limited to 682 poses (2046 unknowns)");
+        }
+    }
+    clear_members(h);
+    h->B = n_members;
+    if (n_members) h->pose_off.assign(pose_off, pose_off + n_members + 1);
+    return SLAM_OK;
+}
+
+int slam_graph_update_members(slam_graph* h, double* stats) {
+    SLAM_ARG_CHECK(h && stats, "slam_graph_update_members: NULL argument");
+    SLAM_ARG_CHECK(h->B > 0 && h->poses,
+                   "slam_graph_update_members: the handle has no members (slam_graph_set_members)");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    return do_update_members(h, std::vector<char>((size_t)h->B, 1), stats);
+}
+
+int slam_graph_optimize_members(slam_graph* h, double delta_sum_th, int32_t max_iter, double* stats,
+                                int32_t* n_iter) {
+    SLAM_ARG_CHECK(h && n_iter && max_iter >= 1, "slam_graph_optimize_members: bad arguments");
+    SLAM_ARG_CHECK(h->B > 0 && h->poses,
+                   "slam_graph_optimize_members: the handle has no members (slam_graph_set_members)");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    const int64_t B = h->B;
+    if (stats) std::fill(stats, stats + 4 * B * (int64_t)max_iter, 0.0);
+    // every member runs the loop of slam_graph_optimize (:692) on its own sum
+    const bool first = delta_sum_th <= delta_sum_th;           // false for a NaN threshold, as there
+    std::vector<char> act((size_t)B, first ? 1 : 0);
+    std::vector<int32_t> it((size_t)B, 0);
+    std::vector<double> st((size_t)(4 * B));
+    for (bool any = first; any;) {
+        GTRY(do_update_members(h, act, st.data()));
+        any = false;
+        for (int64_t m = 0; m < B; ++m) {
+            if (!act[m]) continue;
+            if (stats) std::memcpy(stats + 4 * (m * max_iter + it[m]), &st[4 * m], 4 * sizeof(double));
+            ++it[m];
+            act[m] = (delta_sum_th <= st[4 * m + 1] && it[m] < max_iter) ? 1 : 0;
+            any = any || act[m];
+        }
+    }
+    std::copy(it.begin(), it.end(), n_iter);
+    return SLAM_OK;
+}
+
 int slam_graph_get_system(slam_graph* h, int64_t* n_times, int64_t* times, double* H, double* b,
                           double* blocks) {
     SLAM_ARG_CHECK(h && n_times, "slam_graph_get_system: bad arguments");
@@ -1362,11 +1664,16 @@ int slam_graph_get_system(slam_graph* h, int64_t* n_times, int64_t* times, doubl
     *n_times = h->nt;
     if (times) std::memcpy(times, h->times_h.data(), h->nt * sizeof(int64_t));
     const int64_t n = 3 * h->nt;
+    DeviceMem union_h;             // with members h->A holds their matrices, not the union's
     if (H) {
-        SLAM_ARG_CHECK(h->A, "slam_graph_get_system: dense H only up to 2048 unknowns");
-        GTRY(dense_matrix(h));
-        SLAM_HIP_TRY(hipMemcpyAsync(H, h->A, n * n * sizeof(double), hipMemcpyDeviceToHost,
-                                    h->stream));
+        double* A = h->A;
+        if (h->B) {
+            SLAM_ARG_CHECK(n <= kGraphDenseMax, "slam_graph_get_system: dense H only up to 2048 unknowns");
+            GTRY(union_h.alloc(&A, (size_t)(n * n)));
+        }
+        SLAM_ARG_CHECK(A, "slam_graph_get_system: dense H only up to 2048 unknowns");
+        GTRY(dense_matrix(h, A));
+        SLAM_HIP_TRY(hipMemcpyAsync(H, A, n * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     if (b)
         SLAM_HIP_TRY(hipMemcpyAsync(b, h->b, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1441,6 +1748,7 @@ int slam_graph_marginals(slam_graph* h, int64_t m, const int64_t* times, int32_t
                          double* cov, double* info) {
     SLAM_ARG_CHECK(h && times && cov && info && m >= 1, "slam_graph_marginals: bad arguments");
     SLAM_ARG_CHECK(h->poses, "slam_graph_marginals: set the poses first");
+    SLAM_ARG_CHECK(h->B == 0, "slam_graph_marginals: not on a handle with members");
     SLAM_ARG_CHECK(m <= (int64_t)1 << 20, "slam_graph_marginals: too many times");
     const int64_t M = 3 * m;
     const int cols = h->marg_cols ? h->marg_cols : kMargDefaultCols;
@@ -1547,6 +1855,7 @@ int slam_graph_precond_info(slam_graph* h, double* out) {
 
 int slam_graph_apply_precond(slam_graph* h, const double* r, double* z) {
     SLAM_ARG_CHECK(h && r && z, "slam_graph_apply_precond: NULL argument");
+    SLAM_ARG_CHECK(h->B == 0, "slam_graph_apply_precond: not on a handle with members");
     SLAM_ARG_CHECK(h->assembled && h->nt > 0,
                    "slam_graph_apply_precond: no system assembled since slam_graph_set_edges");
     SLAM_HIP_TRY(hipSetDevice(h->device));

@@ -203,17 +203,14 @@ __device__ __forceinline__ void robust_weight(const double chi2, const double pa
 // MIXED (an edge set with odometry columns behind the landmark ones, DESIGN
 // 8.4): E stays the column stride of blocks and rows, and the lanes stop at
 // n_lm; the default instantiation does not read n_lm.
-template <int KIND, bool MIXED = false>
-__global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
-                                                              const slam_graph_edge* __restrict__ edges,
-                                                              const double* __restrict__ poses,
-                                                              const GraphConst g,
-                                                              double* __restrict__ blocks,
-                                                              const double param,
-                                                              double* __restrict__ rows,
-                                                              const int64_t n_lm) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (MIXED ? n_lm : E)) return;
+// The lane's work for landmark edge e (the one statement of it: this kernel and
+// the member kernel of graph_members.inl call it).
+template <int KIND>
+__device__ __forceinline__ void linearize_edge(const int64_t e, const int64_t E,
+                                               const slam_graph_edge* __restrict__ edges,
+                                               const double* __restrict__ poses,
+                                               const GraphConst& g, double* __restrict__ blocks,
+                                               const double param, double* __restrict__ rows) {
     const slam_graph_edge ed = edges[e];
     const double* xb = poses + 3 * ed.pose_bfr;
     const double* xa = poses + 3 * ed.pose_aft;
@@ -267,6 +264,20 @@ __global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
     }
 }
 
+template <int KIND, bool MIXED = false>
+__global__ __launch_bounds__(256) void graph_linearize_kernel(const int64_t E,
+                                                              const slam_graph_edge* __restrict__ edges,
+                                                              const double* __restrict__ poses,
+                                                              const GraphConst g,
+                                                              double* __restrict__ blocks,
+                                                              const double param,
+                                                              double* __restrict__ rows,
+                                                              const int64_t n_lm) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (MIXED ? n_lm : E)) return;
+    linearize_edge<KIND>(e, E, edges, poses, g, blocks, param, rows);
+}
+
 // ------------------------------------------------------- odometry edges
 // DESIGN 8.4 (no reference counterpart).  The record shares its size and its
 // index prefix with slam_graph_edge, so the concatenated device array feeds the
@@ -310,11 +321,11 @@ __device__ __forceinline__ double odom_chi2(const double* err, const double* om)
 // One lane per odometry edge, over the tail columns [n_lm, E) of the same
 // [42][E] blocks (and of rows, when the handle has a robust kind: chi2_e and
 // w_e = 1 -- an odometry edge is never down-weighted).
-__global__ __launch_bounds__(256) void graph_linearize_odom_kernel(
-    const int64_t n_lm, const int64_t E, const slam_graph_edge* __restrict__ edges,
-    const double* __restrict__ poses, double* __restrict__ blocks, double* __restrict__ rows) {
-    const int64_t e = n_lm + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
+__device__ __forceinline__ void linearize_odom_edge(const int64_t e, const int64_t E,
+                                                    const slam_graph_edge* __restrict__ edges,
+                                                    const double* __restrict__ poses,
+                                                    double* __restrict__ blocks,
+                                                    double* __restrict__ rows) {
     const slam_graph_odom od = reinterpret_cast<const slam_graph_odom*>(edges)[e];
     double err[3], om[3], csd[4];
     odom_err_info(od, poses + 3 * od.pose_bfr, poses + 3 * od.pose_aft, err, om, csd);
@@ -357,6 +368,14 @@ __global__ __launch_bounds__(256) void graph_linearize_odom_kernel(
         acc = fma(JaW[3 * i + 1], err[1], acc);
         put(39 + i, fma(JaW[3 * i + 2], err[2], acc));
     }
+}
+
+__global__ __launch_bounds__(256) void graph_linearize_odom_kernel(
+    const int64_t n_lm, const int64_t E, const slam_graph_edge* __restrict__ edges,
+    const double* __restrict__ poses, double* __restrict__ blocks, double* __restrict__ rows) {
+    const int64_t e = n_lm + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    linearize_odom_edge(e, E, edges, poses, blocks, rows);
 }
 
 // --------------------------------------------------------------- pairing
@@ -412,15 +431,13 @@ __global__ __launch_bounds__(256) void graph_pair_kernel(
 // -------------------------------------------------------------- assemble
 // One lane per (block slot, entry): the slot's contributions in edge order
 // (code = 4 e + part), starting from the anchor on slot 0 (:475).
-__global__ __launch_bounds__(256) void graph_assemble_h_kernel(
-    const int64_t n_slots, const int64_t E, const int64_t* __restrict__ cptr,
-    const int64_t* __restrict__ clist, const double* __restrict__ blocks, const double anchor,
-    double* __restrict__ val) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_slots * 9) return;
-    const int64_t s = t / 9;
-    const int q = (int)(t - s * 9);
-    double acc = (s == 0 && (q == 0 || q == 4 || q == 8)) ? anchor : 0.0;
+// Entry q of slot s: `acc` (the anchor or 0) plus the slot's contributions in
+// edge order -- shared with the member kernel of graph_members.inl.
+__device__ __forceinline__ double assemble_h_entry(const int64_t s, const int q, double acc,
+                                                   const int64_t E,
+                                                   const int64_t* __restrict__ cptr,
+                                                   const int64_t* __restrict__ clist,
+                                                   const double* __restrict__ blocks) {
     // groups of 8 contributions: the codes, then the block entries, are loaded
     // together (a diagonal slot collects ~8 edges); the adds stay in edge order
     const int64_t c1 = cptr[s + 1];
@@ -437,17 +454,27 @@ __global__ __launch_bounds__(256) void graph_assemble_h_kernel(
         for (int u = 0; u < 8; ++u)
             if (code[u] >= 0) acc = acc + v[u];
     }
-    val[t] = acc;
+    return acc;
+}
+
+__device__ __forceinline__ bool diag_entry(const int q) { return q == 0 || q == 4 || q == 8; }
+
+__global__ __launch_bounds__(256) void graph_assemble_h_kernel(
+    const int64_t n_slots, const int64_t E, const int64_t* __restrict__ cptr,
+    const int64_t* __restrict__ clist, const double* __restrict__ blocks, const double anchor,
+    double* __restrict__ val) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_slots * 9) return;
+    const int64_t s = t / 9;
+    const int q = (int)(t - s * 9);
+    val[t] = assemble_h_entry(s, q, (s == 0 && diag_entry(q)) ? anchor : 0.0, E, cptr, clist, blocks);
 }
 
 // b: one lane per (block row, entry); code = 2 e + side (0: bfr, 1: aft).
-__global__ __launch_bounds__(256) void graph_assemble_b_kernel(
-    const int64_t n_rows, const int64_t E, const int64_t* __restrict__ bptr,
-    const int64_t* __restrict__ blist, const double* __restrict__ blocks, double* __restrict__ b) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_rows * 3) return;
-    const int64_t r = t / 3;
-    const int a = (int)(t - r * 3);
+__device__ __forceinline__ double assemble_b_entry(const int64_t r, const int a, const int64_t E,
+                                                   const int64_t* __restrict__ bptr,
+                                                   const int64_t* __restrict__ blist,
+                                                   const double* __restrict__ blocks) {
     double acc = 0.0;
     const int64_t c1 = bptr[r + 1];
     for (int64_t c0 = bptr[r]; c0 < c1; c0 += 8) {
@@ -463,7 +490,16 @@ __global__ __launch_bounds__(256) void graph_assemble_b_kernel(
         for (int u = 0; u < 8; ++u)
             if (code[u] >= 0) acc = acc + v[u];
     }
-    b[t] = acc;
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void graph_assemble_b_kernel(
+    const int64_t n_rows, const int64_t E, const int64_t* __restrict__ bptr,
+    const int64_t* __restrict__ blist, const double* __restrict__ blocks, double* __restrict__ b) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows * 3) return;
+    const int64_t r = t / 3;
+    b[t] = assemble_b_entry(r, (int)(t - r * 3), E, bptr, blist, blocks);
 }
 
 // BSR -> dense (n x n, zeroed beforehand)
@@ -518,10 +554,8 @@ __device__ __forceinline__ void block_sum2_fixed(double& a, double& b, double* s
 // --------------------------------------------------- dense LU (getrf)
 // One workgroup.  A (n x n row-major) is overwritten by L\U, piv[k] = row
 // swapped with k.  out: [0] = sign, [1] = sum log|u_kk|, [2] = 1 if a zero pivot.
-__global__ __launch_bounds__(kGraphThreads) void graph_lu_kernel(double* __restrict__ A,
-                                                                 const int n,
-                                                                 int32_t* __restrict__ piv,
-                                                                 double* __restrict__ out) {
+__device__ __forceinline__ void graph_lu_body(double* __restrict__ A, const int n,
+                                              int32_t* __restrict__ piv, double* __restrict__ out) {
     __shared__ double shv[kGraphThreads / 64];
     __shared__ int shi[kGraphThreads / 64];
     __shared__ int s_p;
@@ -611,10 +645,18 @@ __global__ __launch_bounds__(kGraphThreads) void graph_lu_kernel(double* __restr
     }
 }
 
+__global__ __launch_bounds__(kGraphThreads) void graph_lu_kernel(double* __restrict__ A,
+                                                                 const int n,
+                                                                 int32_t* __restrict__ piv,
+                                                                 double* __restrict__ out) {
+    graph_lu_body(A, n, piv, out);
+}
+
 // x = -(LU)^-1 b (getrs with the pivots), one workgroup.  x may alias nothing.
-__global__ __launch_bounds__(kGraphThreads) void graph_lu_solve_kernel(
-    const double* __restrict__ LU, const int n, const int32_t* __restrict__ piv,
-    const double* __restrict__ b, double* __restrict__ x) {
+__device__ __forceinline__ void graph_lu_solve_body(const double* __restrict__ LU, const int n,
+                                                    const int32_t* __restrict__ piv,
+                                                    const double* __restrict__ b,
+                                                    double* __restrict__ x) {
     const int tid = threadIdx.x;
     for (int i = tid; i < n; i += kGraphThreads) x[i] = b[i];
     __syncthreads();
@@ -641,14 +683,25 @@ __global__ __launch_bounds__(kGraphThreads) void graph_lu_solve_kernel(
     for (int i = tid; i < n; i += kGraphThreads) x[i] = -x[i];
 }
 
+__global__ __launch_bounds__(kGraphThreads) void graph_lu_solve_kernel(
+    const double* __restrict__ LU, const int n, const int32_t* __restrict__ piv,
+    const double* __restrict__ b, double* __restrict__ x) {
+    graph_lu_solve_body(LU, n, piv, b, x);
+}
+
 // S = (A + A^T) / 2
+__device__ __forceinline__ double symmetrize_entry(const double* __restrict__ A, const int64_t n,
+                                                   const int64_t t) {
+    const int64_t i = t / n, j = t % n;
+    return 0.5 * (A[i * n + j] + A[j * n + i]);
+}
+
 __global__ __launch_bounds__(256) void graph_symmetrize_kernel(const double* __restrict__ A,
                                                                const int64_t n,
                                                                double* __restrict__ S) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * n) return;
-    const int64_t i = t / n, j = t % n;
-    S[t] = 0.5 * (A[i * n + j] + A[j * n + i]);
+    S[t] = symmetrize_entry(A, n, t);
 }
 
 // Lanczos with full re-orthogonalisation on the symmetric S (n x n), m = n
@@ -680,7 +733,7 @@ __device__ double kth_eig(const double* al, const double* be, const int m, const
     return 0.5 * (lo + hi);
 }
 
-__global__ __launch_bounds__(kGraphThreads) void graph_lanczos_kernel(
+__device__ __forceinline__ void graph_lanczos_body(
     const double* __restrict__ S, const int n, double* __restrict__ V, double* __restrict__ al,
     double* __restrict__ be, double* __restrict__ h, double* __restrict__ out, const uint64_t seed) {
     __shared__ double sh[kGraphThreads / 64];
@@ -791,6 +844,12 @@ __global__ __launch_bounds__(kGraphThreads) void graph_lanczos_kernel(
         out[0] = fmax(fabs(lmin), fabs(lmax));
         out[1] = amin;
     }
+}
+
+__global__ __launch_bounds__(kGraphThreads) void graph_lanczos_kernel(
+    const double* __restrict__ S, const int n, double* __restrict__ V, double* __restrict__ al,
+    double* __restrict__ be, double* __restrict__ h, double* __restrict__ out, const uint64_t seed) {
+    graph_lanczos_body(S, n, V, al, be, h, out, seed);
 }
 
 // ------------------------------------------------------------------ PCG
@@ -1858,6 +1917,28 @@ __global__ __launch_bounds__(kPcgThreads) void graph_precond_apply_kernel(
 
 // ------------------------------------------------------- pose update
 // updateEstPose :499-502 and the per-workgroup partials of Σδ² (:513), one lane per pose.
+// row i: the pose moves by its delta; returns the row's share of sum delta^2
+__device__ __forceinline__ double pose_update_row(const int64_t i, const int64_t* __restrict__ times,
+                                                  const double* __restrict__ delta,
+                                                  double* __restrict__ poses) {
+    double* p = poses + 3 * times[i];
+    const double d0 = delta[3 * i], d1 = delta[3 * i + 1], d2 = delta[3 * i + 2];
+    p[0] = p[0] + d0;
+    p[1] = p[1] + d1;
+    p[2] = wrap_angle(p[2] + d2);
+    double s = 0.0;
+    s = fma(d0, d0, s);
+    s = fma(d1, d1, s);
+    return fma(d2, d2, s);
+}
+
+// the fold of graph_dsum_kernel: part[k] strided over the 1024 lanes, then the fixed tree
+__device__ __forceinline__ double dsum_fold(const int64_t nparts, const double* part, double* sh) {
+    double s = 0.0;
+    for (int64_t k = threadIdx.x; k < nparts; k += 1024) s += part[k];
+    return block_sum_fixed<1024>(s, sh);
+}
+
 __global__ __launch_bounds__(256) void graph_pose_update_kernel(const int64_t nt,
                                                                 const int64_t* __restrict__ times,
                                                                 const double* __restrict__ delta,
@@ -1866,16 +1947,7 @@ __global__ __launch_bounds__(256) void graph_pose_update_kernel(const int64_t nt
     __shared__ double sh[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double s = 0.0;
-    if (i < nt) {
-        double* p = poses + 3 * times[i];
-        const double d0 = delta[3 * i], d1 = delta[3 * i + 1], d2 = delta[3 * i + 2];
-        p[0] = p[0] + d0;
-        p[1] = p[1] + d1;
-        p[2] = wrap_angle(p[2] + d2);
-        s = fma(d0, d0, s);
-        s = fma(d1, d1, s);
-        s = fma(d2, d2, s);
-    }
+    if (i < nt) s = pose_update_row(i, times, delta, poses);
     s = block_sum_fixed<256>(s, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -1885,9 +1957,7 @@ __global__ __launch_bounds__(1024) void graph_dsum_kernel(const int64_t nparts,
                                                          const double* __restrict__ part,
                                                          double* __restrict__ dsum) {
     __shared__ double sh[16];
-    double s = 0.0;
-    for (int64_t k = threadIdx.x; k < nparts; k += 1024) s += part[k];
-    s = block_sum_fixed<1024>(s, sh);
+    const double s = dsum_fold(nparts, part, sh);
     if (threadIdx.x == 0) *dsum = s;
 }
 

@@ -216,6 +216,7 @@ class TrajectoryEstimator(object):
         self._lm_ids = []
         self._times = []
         self._device = device
+        self._solver, self._robust = solver, robust     # for estimate_trajectories' agreement check
         self._pairs = None          # the pair list estimate_trajectory last handed to the device
         self._odom_sigma = None     # setOdometry: None = no odometry edges (the default)
         self._odom = [None]         # per pose id: the rel of the step that led to it
@@ -376,6 +377,82 @@ class TrajectoryEstimator(object):
             st += list(self._dev.optimize(DELTA_SUM_TH, max_iter - 1))
             self._write_back(sorted(set(times_of(paired)) | set(od_times)))
         return np.array(st, dtype=np.float64).reshape(-1, 4)
+
+
+def estimate_trajectories(estimators, halves, n_landmarks, max_iter=100):
+    """The Gauss-Newton loops of several TrajectoryEstimators in one ensemble on
+    the device, one graph per robot (DeviceGraphEnsemble):
+    ``halves[i]`` and ``n_landmarks[i]`` (or one count for all) are what
+    ``estimators[i].estimate_trajectory`` would be given.  Per estimator the
+    halves are paired, the odometry records of setOdometry follow, and the poses
+    are written back; returns each estimator's stats array.  Each estimator ends
+    as its own ``estimate_trajectory(halves[i], n_landmarks[i], max_iter)`` would
+    have left it, bit for bit (its device handle holds the final poses and the
+    edge set, not yet linearised).  ValueError: an estimator with pairs pending
+    from setPairObs, estimators that differ in solver, device or robust kind, or
+    one with more than 682 poses."""
+    from slamhip.graph import MEMBER_MAX_POSES, DeviceGraphEnsemble
+    estimators = list(estimators)
+    if not estimators or len(halves) != len(estimators):
+        raise ValueError("one list of half-edges per estimator")
+    counts = list(n_landmarks) if np.ndim(n_landmarks) else [n_landmarks] * len(estimators)
+    if len(counts) != len(estimators):
+        raise ValueError("one landmark count per estimator, or one for all")
+    e0 = estimators[0]
+
+    def robust_of(e):
+        r = e._robust
+        return None if r is None or r[0] in (None, "none") else (r[0], float(r[1]))
+
+    for e in estimators:
+        if len(e._rows):
+            raise ValueError("an estimator has pairs pending from setPairObs")
+        if (e._solver, e._device, robust_of(e)) != (e0._solver, e0._device, robust_of(e0)):
+            raise ValueError("the estimators differ in solver, device or robust kind")
+        if len(e._poses) > MEMBER_MAX_POSES:
+            raise ValueError("an estimator has more than %d poses" % MEMBER_MAX_POSES)
+
+    def times_of(edges):
+        return np.unique(np.concatenate([edges["time_bfr"], edges["time_aft"]])).tolist()
+
+    out = [None] * len(estimators)
+    members, who = [], []
+    for i, (e, hv, n_lm) in enumerate(zip(estimators, halves, counts)):
+        rows = [[h.getTime(), h.getRobotPoseId(), h.getObs().getLandMarkId(),
+                 h.getObs().getDist(), h.getObs().getDir(), h.getObs().getOrient()] for h in hv]
+        paired = pair_halves(rows, n_lm, device=e._device)
+        od = e._odom_records()
+        seen = set(e._times)
+        for t in (times_of(paired) if len(paired) else []) + ([] if od is None else times_of(od)):
+            if t not in seen:
+                seen.add(t)
+                e._times.append(t)
+        if len(e._times) * 3 <= 3:                       # estimate_trajectory's leng <= 3 branch
+            e._rows = [_rec_row(r) for r in paired]
+            out[i] = np.zeros((1, 4))
+            continue
+        e._pairs = paired
+        poses = np.array([np.asarray(p, dtype=np.float64).reshape(3) for p in e._poses])
+        members.append((poses, paired, od))
+        who.append(i)
+    if members:
+        ens = DeviceGraphEnsemble(solver=e0._solver, device=e0._device, robust=robust_of(e0))
+        try:
+            ens.set_members(members)
+            stats = ens.optimize(DELTA_SUM_TH, max_iter)
+            new = ens.get_poses()
+        finally:
+            ens.close()
+        for k, i in enumerate(who):
+            e = estimators[i]
+            for t in sorted(e._times):
+                for q in range(3):
+                    e._poses[t][q, 0] = new[k][t, q]
+            e._rows, e._lm_ids, e._times = [], [], []
+            e._upload_poses()
+            e._dev.set_edges(members[k][1], odometry=members[k][2])
+            out[i] = stats[k]
+    return out
 
 
 class Robot(object):

@@ -290,6 +290,9 @@ SIGNATURES = {
     "slam_graph_set_edges_odom": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "slam_graph_update": (C.c_int, [_P, _D]),
     "slam_graph_optimize": (C.c_int, [_P, C.c_double, C.c_int32, _D, _I32]),
+    "slam_graph_set_members": (C.c_int, [_P, C.c_int64, _I64]),
+    "slam_graph_update_members": (C.c_int, [_P, _D]),
+    "slam_graph_optimize_members": (C.c_int, [_P, C.c_double, C.c_int32, _D, _I32]),
     "slam_graph_get_system": (C.c_int, [_P, _I64, _I64, _D, _D, _D]),
     "slam_graph_get_bsr": (C.c_int, [_P, _I64, _I64, _I64, _D]),
     "slam_graph_get_delta": (C.c_int, [_P, _D]),

@@ -345,6 +345,138 @@ class DeviceGraph:
                     cond_decided=GATE_COND.get(int(out[2]), "none"))
 
 
+MEMBER_MAX_POSES = 682      # 2046 unknowns: the dense path's limit (slam_graph_set_members)
+
+
+class DeviceGraphEnsemble:
+    """Many pose graphs of the dense path's size on one GPU, advanced together
+    with one launch per phase (slam_graph_set_members).  Takes
+    DeviceGraph's keywords and composes one DeviceGraph.  Member m is bit for
+    bit what a stand-alone DeviceGraph with the same keywords returns for member
+    m's poses and edges alone."""
+
+    def __init__(self, **kwargs):
+        self._dev = DeviceGraph(**kwargs)
+        self._lib = self._dev._lib
+        self.n_members = 0
+        self._pose_off = np.zeros(1, dtype=np.int64)
+        self._lm_off = np.zeros(1, dtype=np.int64)
+        self._od_off = np.zeros(1, dtype=np.int64)
+
+    def set_robust(self, kind, param=None):
+        """One robust kind for all members (DeviceGraph.set_robust)."""
+        self._dev.set_robust(kind, param)
+
+    def close(self):
+        self._dev.close()
+
+    def set_members(self, members):
+        """``members``: a list of (poses, edges) or (poses, edges, odometry) with
+        member-local times and pose ids, edges and odometry as DeviceGraph.set_edges
+        takes them.  Concatenates them, offsets the indices and hands the union
+        to the handle; per-member results come back in the members' own order."""
+        poses, lm, od = [], [], []
+        for mem in members:
+            p = np.ascontiguousarray(mem[0], dtype=np.float64).reshape(-1, 3)
+            e = mem[1]
+            e = e if (isinstance(e, np.ndarray) and e.dtype == EDGE_DTYPE) else edge_array(e)
+            o = mem[2] if len(mem) > 2 and mem[2] is not None else np.zeros(0, dtype=ODOM_DTYPE)
+            o = o if (isinstance(o, np.ndarray) and o.dtype == ODOM_DTYPE) else odom_array(o)
+            poses.append(p)
+            lm.append(e)
+            od.append(o)
+        if not poses:
+            raise ValueError("an ensemble needs at least one member")
+        pose_off = np.concatenate([[0], np.cumsum([len(p) for p in poses])]).astype(np.int64)
+
+        def shifted(recs):
+            out = []
+            for m, r in enumerate(recs):
+                r = r.copy()
+                for name in ("time_bfr", "pose_bfr", "time_aft", "pose_aft"):
+                    r[name] += pose_off[m]
+                out.append(r)
+            return np.concatenate(out)
+
+        self._dev.set_poses(np.concatenate(poses))
+        check(self._lib.slam_graph_set_members(self._dev._h, len(poses),
+                                               pose_off.ctypes.data_as(C.POINTER(C.c_int64))),
+              "slam_graph_set_members")
+        self.n_members = len(poses)
+        self._pose_off = pose_off
+        self._lm_off = np.concatenate([[0], np.cumsum([len(e) for e in lm])]).astype(np.int64)
+        self._od_off = np.concatenate([[0], np.cumsum([len(o) for o in od])]).astype(np.int64)
+        all_od = shifted(od)
+        self._dev.set_edges(shifted(lm), odometry=all_od if len(all_od) else None)
+
+    def update(self):
+        """One updateEstPose of every member: (B, 4) rows (is_calc, delta_sum,
+        det, cond); a zero row for a member with no edge or a single time."""
+        st = np.zeros((self.n_members, 4))
+        check(self._lib.slam_graph_update_members(self._dev._h, dptr(st)), "slam_graph_update_members")
+        return st
+
+    def optimize(self, delta_sum_th=0.01, max_iter=100):
+        """Every member's Gauss-Newton loop; a member that has stopped is left
+        alone.  Returns a list of (n_iter_m, 4) arrays."""
+        st = np.zeros((self.n_members, max_iter, 4))
+        n = np.zeros(self.n_members, dtype=np.int32)
+        check(self._lib.slam_graph_optimize_members(self._dev._h, float(delta_sum_th), int(max_iter),
+                                                    dptr(st), n.ctypes.data_as(C.POINTER(C.c_int32))),
+              "slam_graph_optimize_members")
+        return [st[m, :n[m]].copy() for m in range(self.n_members)]
+
+    def get_poses(self):
+        p = self._dev.get_poses()
+        return [p[a:b] for a, b in zip(self._pose_off[:-1], self._pose_off[1:])]
+
+    def _rows(self):
+        """Per member the block rows of the union (the ranks of its times)."""
+        nt = C.c_int64(0)
+        check(self._lib.slam_graph_get_system(self._dev._h, C.byref(nt), None, None, None, None),
+              "slam_graph_get_system")
+        times = np.empty(nt.value, dtype=np.int64)
+        check(self._lib.slam_graph_get_system(self._dev._h, C.byref(nt),
+                                              times.ctypes.data_as(C.POINTER(C.c_int64)), None, None,
+                                              None), "slam_graph_get_system")
+        cut = np.searchsorted(times, self._pose_off)
+        return times, cut
+
+    def get_delta(self):
+        """Per member the delta of its last solved update (3 per time of its edges)."""
+        _, cut = self._rows()
+        d = self._dev.get_delta()
+        return [d[3 * a:3 * b] for a, b in zip(cut[:-1], cut[1:])]
+
+    def get_system(self):
+        """Per member (times, H, b) of its last assembled system, times
+        member-local; H is the member's diagonal block of the union's
+        block-sparse H (slam_graph_get_bsr), copied, not recomputed."""
+        times, cut = self._rows()
+        b = self._dev.get_system(dense=False)[2]
+        rows, cols, vals = self._dev.get_bsr()
+        out = []
+        for m, (r0, r1) in enumerate(zip(cut[:-1], cut[1:])):
+            n = int(r1 - r0)
+            H = np.zeros((n, 3, n, 3))
+            sel = (rows >= r0) & (rows < r1)
+            H[rows[sel] - r0, :, cols[sel] - r0, :] = vals[sel]
+            out.append((times[r0:r1] - self._pose_off[m], H.reshape(3 * n, 3 * n), b[3 * r0:3 * r1]))
+        return out
+
+    def edge_weights(self):
+        """Per member (chi2, weight) of its columns in stand-alone order: its
+        landmark pairs, then its odometry edges."""
+        c, w = self._dev.edge_weights()
+        n_lm = int(self._lm_off[-1])
+        out = []
+        for m in range(self.n_members):
+            i = np.concatenate([np.arange(self._lm_off[m], self._lm_off[m + 1]),
+                                n_lm + np.arange(self._od_off[m], self._od_off[m + 1])])
+            out.append((c[i], w[i]))
+        return out
+
+
 GATE_DET = {1: "passed (log-det lower end, estimate with 1000x margin)",
             0: "rejected (log-det upper end, Fischer bound)", 3: "passed (dense LU det)",
             2: "rejected (dense LU det)", -1: "undecided"}
