@@ -1281,6 +1281,64 @@ typedef struct {
  * edges (host, *n_edges records) receives the edge list. */
 int slam_graph_pair_halves(int64_t n_halves, const slam_graph_half* halves, int64_t n_landmarks,
                            int device, int64_t* n_edges, slam_graph_edge* edges);
+/* The landmark map of the trajectory (no reference counterpart).
+ * Conditional on the poses the landmarks are independent, and landmark l is the
+ * information-weighted fusion of the half-edges that observe it.  With (x, y,
+ * theta) the handle's current estimate of half-edge k's pose, (d, dir) its range
+ * and bearing and the handle's r_dist, r_dir:
+ *   ang    = dir + theta - pi/2                (the angle of the pair edges' covariance)
+ *   L_k    = (x + d cos ang, y + d sin ang)
+ *   W_k    = R(ang) diag(1 / (d r_dist)^2, 1 / (d sin r_dir)^2) R(ang)^T
+ *   Lam_l  = sum_k W_k     eta_l = sum_k W_k (L_k - L_k0)     k0: l's first half-edge as recorded
+ *   cov_l  = Lam_l^-1      mean_l = L_k0 + cov_l eta_l
+ *   chi2_k = (L_k - mean_l)^T W_k (L_k - mean_l)      chi2_l = sum_k chi2_k
+ * The measured orientation does not enter (it is the robot's compass reading,
+ * not a property of the landmark): the map is conditional on the estimated
+ * headings.  The covariance is that of the observations alone: the uncertainty
+ * of the poses is NOT in it.  The robust kind does not enter either: every
+ * observation counts fully, and half_chi2 is what shows a mis-identified one.
+ * A landmark seen once has mean = L_k exactly, cov = W_k^-1 and chi2 = 0
+ * exactly; a landmark nobody saw has count 0 and NaN mean, cov and chi2.
+ *
+ * The sums are folded in a fixed shape that depends on the landmark's own count
+ * alone (chunks of 256 half-edges counted from its first, a fixed tree inside a
+ * chunk, the chunks in order; no floating-point atomics): the results are
+ * bit-identical from call to call, and a landmark's mean, cov and chi2 are
+ * bit-identical whatever other landmarks and half-edges are in the set and
+ * wherever its own stand among them, given the same relative order.
+ *
+ * slam_graph_set_observations uploads the half-edges and groups them per
+ * landmark once (stable).  A half-edge whose landmark id lies outside [0,
+ * n_landmarks) is ignored, as slam_graph_pair_halves ignores it; its half_chi2
+ * comes back NaN.  n_halves = 0 clears the observations; slam_graph_set_poses
+ * with a different pose count and slam_graph_set_members drop them.
+ * SLAM_ERR_ARG, checked on the host before any HIP call (the handle is left as
+ * it was): a NULL handle, a negative count, a NULL array with a positive
+ * count, poses not set, a handle that has members (slam_graph_set_members), a
+ * pose index out of range, a non-finite observation, and a distance <= 0.
+ *
+ * slam_graph_landmarks evaluates the map at the current poses: mean [NL][2],
+ * cov [NL][4] row-major, count [NL], chi2 [NL], half_chi2 [n_halves] in input
+ * order; any output may be NULL (with chi2 and half_chi2 both NULL the
+ * chi-square pass is not launched).  SLAM_ERR_ARG for a NULL handle and
+ * without observations.  It moves no pose and leaves slam_graph_get_system,
+ * get_delta, timing, cond_info, gate_info, chi2, the edge weights and the
+ * marginals alone; its arrays are its own (made by the first
+ * slam_graph_set_observations, grow-only, released by slam_graph_destroy).  A
+ * handle that is never given observations allocates nothing for the map,
+ * launches what it launched before and computes the same bits.
+ *
+ * slam_graph_map_timing: out[2] = {device ms of the last evaluation's kernels,
+ * their number}; slam_graph_map_kernel_timing: out[5] = the ms of each, in
+ * launch order (contributions, fold, mean and cov, chi-square fold, chi-square
+ * per landmark; 0 for one that was not launched). */
+int slam_graph_set_observations(slam_graph* h, int64_t n_halves, const slam_graph_half* halves,
+                                int64_t n_landmarks);
+int slam_graph_landmarks(slam_graph* h, double* mean /* [NL][2] */, double* cov /* [NL][4] */,
+                         int64_t* count /* [NL] */, double* chi2 /* [NL] */,
+                         double* half_chi2 /* [n_halves], input order */);
+int slam_graph_map_timing(slam_graph* h, double* out /* [2] */);
+int slam_graph_map_kernel_timing(slam_graph* h, double* out /* [5] */);
 /* One-shot form: poses in/out, stats[4] as slam_graph_update. */
 int slam_graph_linearize_solve(const slam_graph_config* cfg, const slam_graph_edge* edges,
                                int64_t n_edges, double* poses, int64_t n_poses, double* stats,

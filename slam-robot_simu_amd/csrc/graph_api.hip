@@ -21,6 +21,7 @@
 #include "graph_build.inl"
 #include "graph_marginals.inl"
 #include "graph_members.inl"
+#include "graph_map.inl"
 
 using namespace slam;
 
@@ -118,6 +119,22 @@ struct slam_graph {
     double* m_out_host = nullptr;          // pinned [B][kMemberOut], then the B sums
     int64_t m_host_cap = 0;                // members the pinned buffers were sized for
     int64_t m_dense_cap[4] = {0, 0, 0, 0}; // elements of A / LU / S, V, lan, piv the members hold
+    // landmark map (slam_graph_set_observations): its own arena and
+    // events, made by the first slam_graph_set_observations (grow-only); a handle
+    // that never gets observations holds none of it
+    DeviceMem map;
+    char* map_arena = nullptr;
+    size_t map_bytes = 0;
+    bool map_set = false;          // observations stand (for the current pose count)
+    int64_t map_n = 0, map_G = 0, map_NL = 0, map_NC = 0;   // input / grouped half-edges, landmarks, chunks
+    std::vector<int64_t> map_count;        // [NL]
+    int64_t *map_gpose = nullptr, *map_gsrc = nullptr, *map_lstart = nullptr;
+    int64_t *map_coff = nullptr, *map_clm = nullptr, *map_cfirst = nullptr;
+    double *map_gobs = nullptr, *map_term = nullptr, *map_part = nullptr;
+    double *map_mean = nullptr, *map_cov = nullptr, *map_chi2 = nullptr, *map_half = nullptr;
+    hipEvent_t map_ev[6] = {};
+    double map_ms[5] = {0, 0, 0, 0, 0};    // kernels of the last evaluation, in launch order
+    double map_last[2] = {0, 0};           // their total (ms), launches
 };
 
 namespace {
@@ -1527,6 +1544,7 @@ int slam_graph_set_poses(slam_graph* h, int64_t n_poses, const double* poses) {
     SLAM_HIP_TRY(hipSetDevice(h->device));
     if (h->B) clear_members(h);                    // the members go, and their edge set with them
     if (n_poses != h->T) {
+        h->map_set = false;                        // the observations index the poses that go
         h->mem.release(h->poses);
         h->T = 0;
         const int rc = h->mem.alloc(&h->poses, 3 * (size_t)n_poses);
@@ -1616,6 +1634,7 @@ int slam_graph_set_members(slam_graph* h, int64_t n_members, const int64_t* pose
         }
     }
     clear_members(h);
+    if (n_members) h->map_set = false;             // no map of members
     h->B = n_members;
     if (n_members) h->pose_off.assign(pose_off, pose_off + n_members + 1);
     return SLAM_OK;
@@ -1908,6 +1927,181 @@ int slam_graph_get_edge_weights(slam_graph* h, double* chi2, double* weight) {
     if (chi2) SLAM_HIP_TRY(hipMemcpyAsync(chi2, r.lin, row, hipMemcpyDeviceToHost, s));
     if (weight) SLAM_HIP_TRY(hipMemcpyAsync(weight, r.lin + h->E, row, hipMemcpyDeviceToHost, s));
     SLAM_HIP_TRY(hipStreamSynchronize(s));
+    return SLAM_OK;
+}
+
+int slam_graph_set_observations(slam_graph* h, int64_t n_halves, const slam_graph_half* halves,
+                                int64_t n_landmarks) {
+    SLAM_ARG_CHECK(h, "slam_graph_set_observations: NULL handle");
+    SLAM_ARG_CHECK(n_halves >= 0 && n_landmarks >= 0, "slam_graph_set_observations: negative count");
+    SLAM_ARG_CHECK(halves || n_halves == 0,
+                   "slam_graph_set_observations: NULL array with a positive count");
+    SLAM_ARG_CHECK(h->poses, "slam_graph_set_observations: set the poses first");
+    SLAM_ARG_CHECK(h->B == 0, "slam_graph_set_observations: the handle has members (no map of members)");
+    for (int64_t q = 0; q < n_halves; ++q) {
+        const slam_graph_half& d = halves[q];
+        SLAM_ARG_CHECK(d.pose >= 0 && d.pose < h->T,
+                       "slam_graph_set_observations: pose index out of range");
+        SLAM_ARG_CHECK(std::isfinite(d.obs[0]) && std::isfinite(d.obs[1]) && std::isfinite(d.obs[2]),
+                       "slam_graph_set_observations: observation is not finite");
+        SLAM_ARG_CHECK(d.obs[0] > 0.0, "slam_graph_set_observations: distance must be > 0");
+    }
+    h->map_set = false;
+    if (n_halves == 0) return SLAM_OK;
+    // stable grouping by landmark id (counting sort), as slam_graph_pair_halves
+    // groups; each landmark's run cut into chunks counted from its first half-edge
+    const int64_t NL = n_landmarks;
+    std::vector<int64_t> lstart(NL + 1, 0), coff(NL + 1, 0);
+    for (int64_t q = 0; q < n_halves; ++q) {
+        const int64_t l = halves[q].landmark;
+        if (l >= 0 && l < NL) lstart[l + 1]++;
+    }
+    h->map_count.assign(lstart.begin() + 1, lstart.end());
+    for (int64_t l = 0; l < NL; ++l) {
+        coff[l + 1] = coff[l] + (lstart[l + 1] + kMapChunk - 1) / kMapChunk;
+        lstart[l + 1] += lstart[l];
+    }
+    const int64_t G = lstart[NL], NC = coff[NL];
+    std::vector<int64_t> gpose(G), gsrc(G), clm(NC), cfirst(NC);
+    std::vector<double> gobs(2 * G);
+    {
+        std::vector<int64_t> fill(lstart.begin(), lstart.end() - 1);
+        for (int64_t q = 0; q < n_halves; ++q) {
+            const int64_t l = halves[q].landmark;
+            if (l < 0 || l >= NL) continue;
+            const int64_t k = fill[l]++;
+            gpose[k] = halves[q].pose;
+            gsrc[k] = q;
+            gobs[k] = halves[q].obs[0];
+            gobs[G + k] = halves[q].obs[1];
+        }
+    }
+    for (int64_t l = 0; l < NL; ++l)
+        for (int64_t c = coff[l]; c < coff[l + 1]; ++c) {
+            clm[c] = l;
+            cfirst[c] = lstart[l] + (c - coff[l]) * kMapChunk;
+        }
+    const std::vector<double> nan_half(n_halves, std::numeric_limits<double>::quiet_NaN());
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    if (!h->map_ev[0])
+        for (auto& e : h->map_ev) GTRY(h->map.event(&e));
+    auto carve = [&](char* base) {
+        Carver cv{base};
+        h->map_gpose = cv.take<int64_t>(G);
+        h->map_gsrc = cv.take<int64_t>(G);
+        h->map_lstart = cv.take<int64_t>(NL + 1);
+        h->map_coff = cv.take<int64_t>(NL + 1);
+        h->map_clm = cv.take<int64_t>(NC);
+        h->map_cfirst = cv.take<int64_t>(NC);
+        h->map_gobs = cv.take<double>(2 * G);
+        h->map_term = cv.take<double>(kMapTerms * G);
+        h->map_part = cv.take<double>(kMapSums * NC);
+        h->map_mean = cv.take<double>(2 * NL);
+        h->map_cov = cv.take<double>(4 * NL);
+        h->map_chi2 = cv.take<double>(NL);
+        h->map_half = cv.take<double>(n_halves);
+        return cv.off;
+    };
+    const size_t need = carve(nullptr);
+    if (need > h->map_bytes) {
+        h->map.release(h->map_arena);
+        h->map_bytes = 0;
+        GTRY(h->map.alloc(&h->map_arena, need + need / 4));
+        h->map_bytes = need + need / 4;
+    }
+    carve(h->map_arena);
+    GTRY(upload(h, h->map_gpose, gpose));
+    GTRY(upload(h, h->map_gsrc, gsrc));
+    GTRY(upload(h, h->map_lstart, lstart));
+    GTRY(upload(h, h->map_coff, coff));
+    GTRY(upload(h, h->map_clm, clm));
+    GTRY(upload(h, h->map_cfirst, cfirst));
+    GTRY(upload(h, h->map_gobs, gobs));
+    GTRY(upload(h, h->map_half, nan_half));    // the ignored half-edges keep this NaN
+    SLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    h->map_n = n_halves;
+    h->map_G = G;
+    h->map_NL = NL;
+    h->map_NC = NC;
+    h->map_set = true;
+    return SLAM_OK;
+}
+
+int slam_graph_landmarks(slam_graph* h, double* mean, double* cov, int64_t* count, double* chi2,
+                         double* half_chi2) {
+    SLAM_ARG_CHECK(h, "slam_graph_landmarks: NULL handle");
+    SLAM_ARG_CHECK(h->map_set, "slam_graph_landmarks: no observations (slam_graph_set_observations)");
+    SLAM_HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int64_t G = h->map_G, NL = h->map_NL, NC = h->map_NC;
+    const bool want_chi2 = chi2 || half_chi2;
+    int launches = 0;
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[0], s));
+    if (G) {
+        hipLaunchKernelGGL(graph_map_contrib_kernel, dim3(nblk(G)), dim3(256), 0, s, G, h->map_gpose,
+                           h->map_gobs, h->poses, gconst(h->cfg), h->map_term);
+        ++launches;
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[1], s));
+    if (G) {
+        hipLaunchKernelGGL(graph_map_fold_kernel<false>, dim3((unsigned)NC), dim3(kMapChunk), 0, s, G,
+                           NC, h->map_clm, h->map_cfirst, h->map_lstart, h->map_term, h->map_mean,
+                           h->map_gsrc, h->map_part, h->map_half);
+        ++launches;
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[2], s));
+    if (NL) {
+        hipLaunchKernelGGL(graph_map_finish_kernel<false>, dim3(nblk(NL, 64)), dim3(64), 0, s, NL, G, NC,
+                           h->map_coff, h->map_lstart, h->map_part, h->map_term, h->map_mean,
+                           h->map_cov, h->map_chi2);
+        ++launches;
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[3], s));
+    if (want_chi2 && G) {
+        hipLaunchKernelGGL(graph_map_fold_kernel<true>, dim3((unsigned)NC), dim3(kMapChunk), 0, s, G,
+                           NC, h->map_clm, h->map_cfirst, h->map_lstart, h->map_term, h->map_mean,
+                           h->map_gsrc, h->map_part, h->map_half);
+        ++launches;
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[4], s));
+    if (want_chi2 && NL) {
+        hipLaunchKernelGGL(graph_map_finish_kernel<true>, dim3(nblk(NL, 64)), dim3(64), 0, s, NL, G, NC,
+                           h->map_coff, h->map_lstart, h->map_part, h->map_term, h->map_mean,
+                           h->map_cov, h->map_chi2);
+        ++launches;
+    }
+    SLAM_HIP_TRY(hipEventRecord(h->map_ev[5], s));
+    SLAM_HIP_TRY(hipGetLastError());
+    const size_t d = sizeof(double);
+    if (mean && NL) SLAM_HIP_TRY(hipMemcpyAsync(mean, h->map_mean, 2 * NL * d, hipMemcpyDeviceToHost, s));
+    if (cov && NL) SLAM_HIP_TRY(hipMemcpyAsync(cov, h->map_cov, 4 * NL * d, hipMemcpyDeviceToHost, s));
+    if (chi2 && NL) SLAM_HIP_TRY(hipMemcpyAsync(chi2, h->map_chi2, NL * d, hipMemcpyDeviceToHost, s));
+    if (half_chi2)
+        SLAM_HIP_TRY(hipMemcpyAsync(half_chi2, h->map_half, h->map_n * d, hipMemcpyDeviceToHost, s));
+    SLAM_HIP_TRY(hipStreamSynchronize(s));
+    if (count) std::copy(h->map_count.begin(), h->map_count.end(), count);
+    double total = 0.0;
+    for (int k = 0; k < 5; ++k) {
+        float ms = 0.f;
+        SLAM_HIP_TRY(hipEventElapsedTime(&ms, h->map_ev[k], h->map_ev[k + 1]));
+        h->map_ms[k] = ms;
+        total += ms;
+    }
+    h->map_last[0] = total;
+    h->map_last[1] = launches;
+    return SLAM_OK;
+}
+
+int slam_graph_map_timing(slam_graph* h, double* out) {
+    SLAM_ARG_CHECK(h && out, "slam_graph_map_timing: NULL argument");
+    out[0] = h->map_last[0];
+    out[1] = h->map_last[1];
+    return SLAM_OK;
+}
+
+int slam_graph_map_kernel_timing(slam_graph* h, double* out) {
+    SLAM_ARG_CHECK(h && out, "slam_graph_map_kernel_timing: NULL argument");
+    for (int k = 0; k < 5; ++k) out[k] = h->map_ms[k];
     return SLAM_OK;
 }
 

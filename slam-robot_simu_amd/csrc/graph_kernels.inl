@@ -51,15 +51,27 @@ __device__ __forceinline__ void mat3_tmul(const double* A, const double* B, doub
         }
 }
 
+// The range and bearing variances of one observation and the angle of its
+// covariance in the world (graph_based_slam.py:175-215): the one statement of
+// both, shared by meas_cov_world and the landmark map (graph_map.inl).
+__device__ __forceinline__ void meas_var_angle(const double dist, const double dir,
+                                               const double yaw, const GraphConst& g, double& v0,
+                                               double& v1, double& ang) {
+    const double dd = dist * g.r_dist;
+    const double sd = dist * sin(g.r_dir);
+    v0 = dd * dd;
+    v1 = sd * sd;
+    ang = dir + yaw - kHalfPi;
+}
+
 // ScanSensor.getLandMarkCovMatrixOnMeasurementSys + tfMeasurement2World
 // (graph_based_slam.py:175-215): R(ang) diag(v) R(ang)^T, ang = dir + yaw - pi/2.
 __device__ __forceinline__ void meas_cov_world(const double dist, const double dir,
                                                const double yaw, const GraphConst& g,
                                                double* C) {
-    const double dd = dist * g.r_dist;
-    const double sd = dist * sin(g.r_dir);
-    const double v0 = dd * dd, v1 = sd * sd, v2 = g.r_dir * g.r_dir + g.r_orient * g.r_orient;
-    const double ang = dir + yaw - kHalfPi;
+    double v0, v1, ang;
+    meas_var_angle(dist, dir, yaw, g, v0, v1, ang);
+    const double v2 = g.r_dir * g.r_dir + g.r_orient * g.r_orient;
     double s, c;
     sincos(ang, &s, &c);
     // (R D) R^T with the structural zeros of R and D dropped (they add exact zeros)

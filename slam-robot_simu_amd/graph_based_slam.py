@@ -21,7 +21,9 @@ stream in the reference's draw order.
 ``estimate_trajectory(halves, n_landmarks)`` is Robot.estimateOpticalTrajectory
 (:685-715): all 2-combinations of each landmark's half-edges, then
 Gauss-Newton until sum(delta^2) < 0.01, with the poses resident on the GPU
-between iterations.
+between iterations.  It keeps the half-edges; ``getEstLandMarks()`` (no
+reference counterpart) then returns the landmark map at the current estimates
+(DESIGN 8.7), and ``Robot.drawEstLandMarks(ax)`` draws it.
 
 ``Robot`` (:584-897) is the reference's driver: ``move(v, w)`` (motion with
 and without noise through the MotionModel drop-in, a scan of the noisy pose,
@@ -220,6 +222,8 @@ class TrajectoryEstimator(object):
         self._pairs = None          # the pair list estimate_trajectory last handed to the device
         self._odom_sigma = None     # setOdometry: None = no odometry edges (the default)
         self._odom = [None]         # per pose id: the rel of the step that led to it
+        self._map_halves = None     # the half-edge rows and landmark count of the last
+        self._map_n_landmarks = 0   # estimate_trajectory (getEstLandMarks)
         self._dev = DeviceGraph(solver=solver, device=device, robust=robust)
 
     def setOdometry(self, sigma):
@@ -306,6 +310,22 @@ class TrajectoryEstimator(object):
         n = len(self._pairs)        # the landmark pairs come first; odometry edges follow
         return self._pairs, chi2[:n], weight[:n]
 
+    def getEstLandMarks(self):
+        """The landmark map at the current pose estimates: {id:
+        (mean (2,), cov (2, 2), count, chi2)} for every landmark that the
+        half-edges of the last ``estimate_trajectory`` saw -- each the
+        information-weighted fusion of its observations given the estimated
+        poses (the covariance does not contain the poses' uncertainty; chi2 is
+        the sum over its observations).  None before any ``estimate_trajectory``."""
+        if self._map_halves is None:
+            return None
+        if not self._map_halves:
+            return {}
+        self._upload_poses()
+        self._dev.set_observations(self._map_halves, self._map_n_landmarks)
+        mean, cov, count, chi2 = self._dev.landmarks()
+        return {int(l): (mean[l], cov[l], int(count[l]), float(chi2[l])) for l in np.flatnonzero(count)}
+
     def _upload_poses(self):
         self._dev.set_poses(np.array([np.asarray(p, dtype=np.float64).reshape(3) for p in self._poses]))
 
@@ -341,6 +361,7 @@ class TrajectoryEstimator(object):
         rows = [[h.getTime(), h.getRobotPoseId(), h.getObs().getLandMarkId(),
                  h.getObs().getDist(), h.getObs().getDir(), h.getObs().getOrient()] for h in halves]
         paired = pair_halves(rows, n_landmarks, device=self._device)     # on the device
+        self._map_halves, self._map_n_landmarks = rows, int(n_landmarks)
 
         def times_of(edges):
             return np.unique(np.concatenate([edges["time_bfr"], edges["time_aft"]])).tolist()
@@ -527,6 +548,11 @@ class Robot(object):
         (TrajectoryEstimator.getEstTrajCov)."""
         return self._est.getEstTrajCov()
 
+    def getEstLandMarks(self):
+        """{id: (mean (2,), cov (2, 2), count, chi2)} of the landmarks seen, at
+        the estimated poses, or None (TrajectoryEstimator.getEstLandMarks)."""
+        return self._est.getEstLandMarks()
+
     # ---------------------------------------------------------- drawing
     def draw(self, aAx1, aAx2, ellipses=False):
         """:717-724: the world frame (ax1) and the robot frame (ax2);
@@ -535,6 +561,19 @@ class Robot(object):
         if ellipses:
             self._draw_est_ellipses(aAx1)
         self._draw_robot_frame(aAx2)
+
+    def drawEstLandMarks(self, ax):
+        """The estimated landmarks and their error ellipses into the world frame
+        (after ``draw``; its signature is pinned, so this is a call of its own)."""
+        from mylib import plots
+        est = self.getEstLandMarks()
+        if not est:
+            return
+        pts = np.array([m for m, _, _, _ in est.values()])
+        plots.landmark_stars(ax, pts[:, 0], pts[:, 1], face="cyan", edge="blue",
+                             label="Land Mark(Estimated)")
+        for m, cov, _, _ in est.values():
+            plots.error_ellipse(ax, (m[0], m[1]), self._ellipse, cov)
 
     def _draw_est_ellipses(self, ax):
         from mylib import plots

@@ -310,6 +310,10 @@ SIGNATURES = {
     "slam_graph_linearize_solve": (C.c_int, [C.POINTER(GraphConfig), _P, C.c_int64, _D, C.c_int64,
                                              _D, C.c_int]),
     "slam_graph_pair_halves": (C.c_int, [C.c_int64, _P, C.c_int64, C.c_int, _I64, _P]),
+    "slam_graph_set_observations": (C.c_int, [_P, C.c_int64, _P, C.c_int64]),
+    "slam_graph_landmarks": (C.c_int, [_P, _D, _D, _I64, _D, _D]),
+    "slam_graph_map_timing": (C.c_int, [_P, _D]),
+    "slam_graph_map_kernel_timing": (C.c_int, [_P, _D]),
 }
 
 _lib = None

@@ -22,19 +22,25 @@ ODOM_DTYPE = np.dtype([("time_bfr", "<i8"), ("pose_bfr", "<i8"), ("time_aft", "<
 HALF_DTYPE = np.dtype([("time", "<i8"), ("pose", "<i8"), ("landmark", "<i8"), ("obs", "<f8", (3,))])
 
 
-def pair_halves(halves, n_landmarks, device=0):
-    """Robot.estimateOpticalTrajectory's pairing (graph_based_slam.py:697-703)
-    on the device: ``halves`` rows [time, pose_id, landmark, dist, dir, orient]
-    (or HALF_DTYPE records) in recording order -> slam_graph_edge records, in
-    the reference's order (landmark, then itertools.combinations), each pair
-    ordered as setPairObs orders it (:371-384)."""
+def half_array(halves):
+    """Half-edge rows [time, pose_id, landmark, dist, dir, orient] (or HALF_DTYPE
+    records) -> contiguous slam_graph_half records."""
     if not (isinstance(halves, np.ndarray) and halves.dtype == HALF_DTYPE):
         rows = np.asarray(halves, dtype=np.float64).reshape(-1, 6)
         rec = np.zeros(len(rows), dtype=HALF_DTYPE)
         rec["time"], rec["pose"], rec["landmark"] = rows[:, 0], rows[:, 1], rows[:, 2]
         rec["obs"] = rows[:, 3:6]
         halves = rec
-    halves = np.ascontiguousarray(halves)
+    return np.ascontiguousarray(halves)
+
+
+def pair_halves(halves, n_landmarks, device=0):
+    """Robot.estimateOpticalTrajectory's pairing (graph_based_slam.py:697-703)
+    on the device: ``halves`` rows [time, pose_id, landmark, dist, dir, orient]
+    (or HALF_DTYPE records) in recording order -> slam_graph_edge records, in
+    the reference's order (landmark, then itertools.combinations), each pair
+    ordered as setPairObs orders it (:371-384)."""
+    halves = half_array(halves)
     lib = _lib.load()
     n = C.c_int64(0)
     check(lib.slam_graph_pair_halves(len(halves), halves.ctypes.data_as(C.c_void_p),
@@ -112,6 +118,8 @@ class DeviceGraph:
         self.n_poses = 0
         self.n_edges = 0
         self.n_odom = 0
+        self.n_halves = 0           # observations of the landmark map (set_observations)
+        self.n_landmarks = 0
         if robust is not None:
             try:
                 self.set_robust(*robust)
@@ -199,6 +207,44 @@ class DeviceGraph:
               "slam_graph_get_edge_weights")
         return c, w
 
+    def set_observations(self, halves, n_landmarks):
+        """The observations of the landmark map (slam_graph_set_observations;
+        DESIGN 8.7): HALF_DTYPE records or rows [time, pose_id, landmark, dist,
+        dir, orient], as ``pair_halves`` takes them, grouped per landmark once.
+        A landmark id outside [0, n_landmarks) is ignored.  No half-edge clears
+        them; ``set_poses`` with another pose count drops them."""
+        rec = half_array(halves)
+        check(self._lib.slam_graph_set_observations(self._h, len(rec), rec.ctypes.data_as(C.c_void_p),
+                                                    int(n_landmarks)), "slam_graph_set_observations")
+        self.n_halves, self.n_landmarks = len(rec), int(n_landmarks)
+
+    def landmarks(self, per_observation=False):
+        """The landmark map at the current poses (slam_graph_landmarks): (mean
+        (NL, 2), cov (NL, 2, 2), count (NL,), chi2 (NL,)), and with
+        ``per_observation=True`` the chi-square of every half-edge in input order
+        (NaN for an ignored one).  Each landmark is the information-weighted
+        fusion of its observations given the poses; the covariance does not
+        contain the uncertainty of the poses.  NaN where count is 0.  Moves
+        nothing."""
+        nl = self.n_landmarks
+        mean, cov, chi2 = np.empty((nl, 2)), np.empty((nl, 2, 2)), np.empty(nl)
+        count = np.zeros(nl, dtype=np.int64)
+        half = np.empty(self.n_halves) if per_observation else None
+        check(self._lib.slam_graph_landmarks(self._h, dptr(mean), dptr(cov),
+                                             count.ctypes.data_as(C.POINTER(C.c_int64)), dptr(chi2),
+                                             dptr(half)), "slam_graph_landmarks")
+        return (mean, cov, count, chi2, half) if per_observation else (mean, cov, count, chi2)
+
+    def map_timing(self):
+        """Device time of the last ``landmarks`` (slam_graph_map_timing and
+        slam_graph_map_kernel_timing): the kernels' total, their number, and the
+        ms of each in launch order."""
+        out, ker = np.zeros(2), np.zeros(5)
+        check(self._lib.slam_graph_map_timing(self._h, dptr(out)), "slam_graph_map_timing")
+        check(self._lib.slam_graph_map_kernel_timing(self._h, dptr(ker)), "slam_graph_map_kernel_timing")
+        return dict(ms=out[0], launches=int(out[1]), contrib_ms=ker[0], fold_ms=ker[1], finish_ms=ker[2],
+                    chi2_fold_ms=ker[3], chi2_finish_ms=ker[4])
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.slam_graph_destroy(self._h)
@@ -209,6 +255,8 @@ class DeviceGraph:
     def set_poses(self, poses):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
         check(self._lib.slam_graph_set_poses(self._h, len(poses), dptr(poses)), "slam_graph_set_poses")
+        if len(poses) != self.n_poses:
+            self.n_halves = self.n_landmarks = 0    # the handle dropped the observations
         self.n_poses = len(poses)
 
     def get_poses(self):
@@ -485,14 +533,10 @@ GATE_COND = {1: "passed (estimate with margin)", 0: "rejected (estimate: for cer
              3: "passed (dense Lanczos cond)", 2: "rejected (dense Lanczos cond)", -1: "undecided"}
 
 
-def circle_graph(n_poses, n_landmarks=64, loops_per_pose=3, seed=0, odom_noise=0.02):
-    """Synthetic pose graph of the graph_based_slam.py form (BASELINE config 5):
-    a robot circling at 10 m radius with a ScanSensor (15 m, +-80 deg,
-    :899-902) among ``n_landmarks`` landmarks on a 14 m ring; one edge per
-    consecutive pose pair sharing a landmark and ``loops_per_pose`` loop edges
-    per pose between observations of the same landmark at other times.
-    Returns (initial pose estimates (T,3), true poses (T,3), edge records)."""
-    rs = np.random.RandomState(seed)
+def _circle_world(n_poses, n_landmarks, rs):
+    """circle_graph's world: (true poses (T,3), landmarks (NL,2), visibility
+    (T,NL), noisy (distance, direction, orientation) (T,NL,3)); three arrays of
+    standard normals drawn from ``rs`` in that order."""
     step = np.deg2rad(10.0)
     ang = np.arange(n_poses) * step
     truth = np.column_stack([10 * np.cos(ang), 10 * np.sin(ang),
@@ -512,6 +556,18 @@ def circle_graph(n_poses, n_landmarks=64, loops_per_pose=3, seed=0, odom_noise=0
                     bearing + np.deg2rad(2.0) * rs.standard_normal(dist.shape),
                     orient + np.deg2rad(2.0) * rs.standard_normal(dist.shape)], -1)
     obs[..., 1:] = np.mod(obs[..., 1:] + np.pi, 2 * np.pi) - np.pi
+    return truth, lm, vis, obs
+
+
+def circle_graph(n_poses, n_landmarks=64, loops_per_pose=3, seed=0, odom_noise=0.02):
+    """Synthetic pose graph of the graph_based_slam.py form (BASELINE config 5):
+    a robot circling at 10 m radius with a ScanSensor (15 m, +-80 deg,
+    :899-902) among ``n_landmarks`` landmarks on a 14 m ring; one edge per
+    consecutive pose pair sharing a landmark and ``loops_per_pose`` loop edges
+    per pose between observations of the same landmark at other times.
+    Returns (initial pose estimates (T,3), true poses (T,3), edge records)."""
+    rs = np.random.RandomState(seed)
+    truth, _, vis, obs = _circle_world(n_poses, n_landmarks, rs)
     seen_by = [np.flatnonzero(vis[:, j]) for j in range(n_landmarks)]
     rows = []
 
@@ -541,6 +597,20 @@ def circle_graph(n_poses, n_landmarks=64, loops_per_pose=3, seed=0, odom_noise=0
     init = truth + np.cumsum(odom_noise * rs.standard_normal(truth.shape), axis=0)
     init[:, 2] = np.mod(init[:, 2] + np.pi, 2 * np.pi) - np.pi
     return init, truth, rec
+
+
+def circle_graph_halves(n_poses, n_landmarks=64, seed=0, odom_noise=0.02):
+    """circle_graph's world with every visible landmark a half-edge (time = pose
+    id, recording order: by pose, then by landmark id).  Returns (initial pose
+    estimates (T,3), true poses (T,3), HALF_DTYPE records, landmarks (NL,2))."""
+    rs = np.random.RandomState(seed)
+    truth, lm, vis, obs = _circle_world(n_poses, n_landmarks, rs)
+    t, j = np.nonzero(vis)
+    rec = np.zeros(len(t), dtype=HALF_DTYPE)
+    rec["time"], rec["pose"], rec["landmark"], rec["obs"] = t, t, j, obs[t, j]
+    init = truth + np.cumsum(odom_noise * rs.standard_normal(truth.shape), axis=0)
+    init[:, 2] = np.mod(init[:, 2] + np.pi, 2 * np.pi) - np.pi
+    return init, truth, rec, lm
 
 
 def circle_graph_odometry(truth, sigma, seed):
