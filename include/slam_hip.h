@@ -126,6 +126,33 @@ int slam_pf_weight_sum(slam_pf* h, double* sum_out);
  * / Philox-2x32-10 + Box-Muller; not a reference interface), out: count x 6. */
 int slam_debug_pair_normals(int device, uint64_t p0, int64_t count, uint32_t rstep, uint64_t seed,
                             double* out);
+/* Diagnostics: one routine of csrc/fastmath.hpp run on the device, one lane per
+ * argument, through the inline function the production kernels call (tables in
+ * LDS as production stages them; not a reference interface).  in: n x 4
+ * operands, out: n x 2 results; unused operands are ignored, unused results 0.
+ *   sin/cos routines:  in (x), out (sin, cos)
+ *   ROTATE_SC:         in (s, c, sd, cd), out (sin, cos) of the sum
+ *   exp / sqrt:        in (x), out (value)
+ *   RNG_*_TAB, RNG_SINCOS2PI: in (the 32-bit word as a double); the uniform is
+ *                      (word + 1) 2^-32 as in the Box-Muller pair
+ *   RNG_LOG_SCALED:    in (d, e), out log(d 2^e) */
+enum { SLAM_MATH_FAST_SINCOS = 0,
+       SLAM_MATH_SMALL_SINCOS = 1,
+       SLAM_MATH_ROTATE_SC = 2,
+       SLAM_MATH_HEADING_SINCOS_TAB = 3,
+       SLAM_MATH_EXP_LEAN = 4,
+       SLAM_MATH_EXP_TAB = 5,            /* exp_tab<false> */
+       SLAM_MATH_EXP_TAB_NONPOS = 6,     /* exp_tab<true> */
+       SLAM_MATH_EXP_NHALF = 7,          /* exp_nhalf<false> */
+       SLAM_MATH_EXP_NHALF_NONPOS = 8,   /* exp_nhalf<true> */
+       SLAM_MATH_SQRT_POS = 9,
+       SLAM_MATH_RNG_LOG_TAB = 10,
+       SLAM_MATH_RNG_SINCOS2PI_TAB = 11,
+       SLAM_MATH_RNG_LOG_SCALED = 12,
+       SLAM_MATH_RNG_SINCOS2PI = 13,
+       SLAM_MATH_COUNT = 14 };
+int slam_debug_math(int device, int32_t fn, int64_t n, const double* in /* n x 4 */,
+                    double* out /* n x 2 */);
 /* Diagnostics: what this library holds in this process right now, over all
  * handles and the stateless entry points' scratch: out[0] device bytes, out[1]
  * pinned host bytes, out[2] events.  Exact counts kept by the library's one

@@ -91,7 +91,8 @@ __device__ __forceinline__ void philox2x32(uint32_t& c0, uint32_t& c1, uint32_t 
 // One Box-Muller pair from two 32-bit words: uniforms (a + 1) 2^-32 and
 // (b + 1) 2^-32 in (0, 1] (radius resolution 2^-32: |g| <= 6.66, a tail mass of
 // 3e-11 per draw); log and sin/cos from the LDS tables of fastmath.hpp
-// (rng_log_tab, rng_sincos2pi_tab: < 1.5 ulp), sqrt_pos.
+// (rng_log_tab: <= 1.3 ulp; rng_sincos2pi_tab: < 1.5 ulp of 1, i.e. an absolute
+// 1.5 2^-53 -- not relative to a result near zero), sqrt_pos.
 __device__ __forceinline__ void bm_pair(uint32_t a, uint32_t b, const RngTabs& T, double& gc,
                                         double& gs) {
 #ifdef SLAM_RNG_NO_TABLES                                   // A/B diagnostic: the round-2 forms

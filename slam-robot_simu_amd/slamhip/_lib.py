@@ -129,6 +129,12 @@ _I64 = C.POINTER(C.c_int64)
 _I32 = C.POINTER(C.c_int32)
 _U32 = C.POINTER(C.c_uint32)
 
+# slam_debug_math's fn (the SLAM_MATH_* enum of slam_hip.h)
+MATH_FN = {name: k for k, name in enumerate((
+    "fast_sincos", "small_sincos", "rotate_sc", "heading_sincos_tab", "exp_lean", "exp_tab",
+    "exp_tab_nonpos", "exp_nhalf", "exp_nhalf_nonpos", "sqrt_pos", "rng_log_tab",
+    "rng_sincos2pi_tab", "rng_log_scaled", "rng_sincos2pi"))}
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "slam_version": (C.c_int, []),
@@ -148,6 +154,7 @@ SIGNATURES = {
     "slam_pf_resample_indices": (C.c_int, [_P, C.c_double, _I64, _I32]),
     "slam_pf_weight_sum": (C.c_int, [_P, _D]),
     "slam_debug_pair_normals": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_uint32, C.c_uint64, _D]),
+    "slam_debug_math": (C.c_int, [C.c_int, C.c_int32, C.c_int64, _D, _D]),
     "slam_debug_live_resources": (C.c_int, [_I64]),
     "slam_pf_load_observations": (C.c_int, [_P, C.c_int32, _D]),
     "slam_pf_run": (C.c_int, [_P, C.c_int32, C.c_int32, _D, C.POINTER(PFResult)]),

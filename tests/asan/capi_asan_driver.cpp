@@ -98,6 +98,12 @@ int main() {
     EXPECT_ERR(slam_pf_load_truth(nullptr, 4, buf.data()));
     EXPECT_ERR(slam_pf_step_truth(nullptr, buf.data(), buf.data(), buf.data(), &res));
     EXPECT_ERR(slam_debug_pair_normals(0, 0, -1, 0, 0, buf.data()));
+    EXPECT_ERR(slam_debug_math(0, SLAM_MATH_EXP_TAB, -1, buf.data(), buf.data()));
+    EXPECT_ERR(slam_debug_math(0, SLAM_MATH_EXP_TAB, 4, nullptr, buf.data()));
+    EXPECT_ERR(slam_debug_math(0, SLAM_MATH_EXP_TAB, 4, buf.data(), nullptr));
+    EXPECT_ERR(slam_debug_math(0, -1, 4, buf.data(), buf.data()));
+    EXPECT_ERR(slam_debug_math(0, SLAM_MATH_COUNT, 4, buf.data(), buf.data()));
+    CHECK(slam_debug_math(0, SLAM_MATH_EXP_TAB, 0, buf.data(), buf.data()) == 0, "debug_math: n = 0 is a no-op");
 
     // ---- the sharded filter
     int64_t gb = -1, nl = -1, sum = 0;

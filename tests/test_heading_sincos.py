@@ -11,39 +11,14 @@ fdlibm kernels, three-part reduction) is < 1 ulp; the
 predict's parity bars (tests/test_gpu_c2.py: 1e-12 (|ref| + |v/w|)) sit
 four orders above either."""
 import math
-import pathlib
-import re
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
+from fastmath_ref import heading_sincos_tab          # the restatement, operation by operation
+from fastmath_ref import sincos_table as _table
+
 mp = pytest.importorskip("mpmath")
-HEX = r"-?0x[0-9a-fA-F.]+p[-+]?\d+"
-
-
-def _table():
-    src = (ROOT / "slam-robot_simu_amd/csrc/fastmath.hpp").read_text()
-    m = re.search(r"kRngSinCos256\[256\] = \{(.*?)\n\};", src, re.S)
-    v = [float.fromhex(x) for x in re.findall(HEX, m.group(1))]
-    return [(v[2 * k], v[2 * k + 1]) for k in range(256)]
-
-
-def fma(a, b, c):
-    return float(Fraction(a) * Fraction(b) + Fraction(c))
-
-
-def heading_sincos_tab(x, T):
-    k128pi = 40.74366543152521
-    hi, lo = float.fromhex("0x1.921fb54442dp-6"), float.fromhex("0x1.8469898cc5170p-54")
-    j = float(np.rint(x * k128pi))
-    r = fma(-j, lo, fma(-j, hi, x))
-    ts, tc = T[int(j) & 255]
-    z = r * r
-    sr = fma(r * z, fma(z, fma(z, -1.0 / 5040.0, 1.0 / 120.0), -1.0 / 6.0), r)
-    cr = fma(z, fma(z, fma(z, -1.0 / 720.0, 1.0 / 24.0), -0.5), 1.0)
-    return fma(ts, cr, tc * sr), fma(tc, cr, -(ts * sr))
 
 
 def test_constants_split_pi_over_128():
